@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Benchmark of the Faster R-CNN hot path on MI355X (BASELINE.json metric: images/sec, VGG16, 600x1000).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`): nothing else.  `--full` adds every
+secondary measurement and check described below (stage events, roofline, isolated RoI / proposal graphs, the input-fed and two-in-flight
+forms, the bf16 / f16 / split-product variants, the CPU baseline and parity; in the training modes the CPU baseline and the step without
+ProposalLayer).  `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 N>1: the driver launches `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`; a plain
 `python bench.py --gpus N` re-launches itself that way (one rank per GPU; with fewer GPUs than ranks the ranks share GPUs over
 gloo -- a functional smoke of the N>1 path, said so in the line).
@@ -36,6 +41,40 @@ SUSTAINED_BF16_MFMA_TFLOPS_RANDOM = 1867.0   # measured, round 3: every SIMD iss
 PEAK_HBM_GBPS = 8000.0            # MI355X_MICROARCH.md: HBM3E peak BW (spec)
 IM_H, IM_W = 600, 1000
 DEFAULT_STEPS = 250               # ~1 s of timed region at 3.9 ms / step: long enough for an outside observer (rocm-smi) to see it
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: at most 64 MiB in all
+DUMP_SAMPLE = 1 << 20             # elements of a fixed, seeded sample of a flat buffer too large to dump whole
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (host NumPy arrays; integer ones widened to float64), at most DUMP_LIMIT_BYTES in all."""
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(out)
+
+
+def flat_sample(torch, flat):
+    """A fixed, seeded sample (at most DUMP_SAMPLE distinct elements, sorted indices) of a large flat device buffer, gathered on the device."""
+    n = int(flat.numel())
+    if n <= DUMP_SAMPLE:
+        return flat.detach().cpu().numpy()
+    idx = np.unique(np.random.RandomState(0).randint(0, n, DUMP_SAMPLE))
+    return flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+
+def inference_outputs(rt, out):
+    """What a caller of the forward receives: the n_out valid rows of cls_prob / pred_boxes / rois / probs, and n_out."""
+    n = int(rt.mem.to_numpy(out["n_out"]).reshape(-1)[0])
+    res = {k: rt.mem.to_numpy(out[k])[:n] for k in ("cls_prob", "pred_boxes", "rois", "probs")}
+    res["n_out"] = np.array([n], np.float64)
+    return res
 
 
 class EventTimer(object):
@@ -742,9 +781,12 @@ def train_mode(args, torch, dist, rt, model, x, rank, world, barrier, shared_not
         mark("update")
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"losses": rt.mem.to_numpy(out["losses"]), "weights_sample": flat_sample(torch, tr.W),
+                                         "gradients_sample": flat_sample(torch, tr.G)})
     # the same K steps without the (discarded) ProposalLayer launch sequence, for the record
     other_ms = None
-    if not args.no_train_proposals:
+    if args.full and not args.no_train_proposals:
         tr.run_proposal_layer = False
         for _ in range(2):
             tr.step(x, info, gt_dev)
@@ -765,7 +807,7 @@ def train_mode(args, torch, dist, rt, model, x, rank, world, barrier, shared_not
         if conv_math == "split":
             roof["basis"] += "; the forward / input-gradient products run on the bf16 pipes (six per fp32 product): the fraction is of the fp32 MFMA peak and may exceed what fp32 MFMAs could do"
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and params is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and params is not None:
             try:
                 cpu = cpu_train_baseline(params, x_host, gt, stage2=False, samples=3, warmups=1, rank_seed=rank)
             except Exception as e:
@@ -835,6 +877,11 @@ def train_rcnn_mode(args, torch, dist, rt, model, x, rank, world, barrier, share
         hook("update")
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        n = int(out["n_rois"])
+        dump_outputs(args.dump_outputs, {"losses": rt.mem.to_numpy(out["losses"]), "rois": rt.mem.to_numpy(out["rois"])[:n],
+                                         "keep_inds": rt.mem.to_numpy(out["keep_inds"]), "weights_sample": flat_sample(torch, tr.W),
+                                         "gradients_sample": flat_sample(torch, tr.G)})
     dt, per_rank = gather_rank_times(torch, dist, dt, world)
     if rank == 0:
         names = [n for n, _, _ in ev[0]]
@@ -848,7 +895,7 @@ def train_rcnn_mode(args, torch, dist, rt, model, x, rank, world, barrier, share
                               sum(v for k, v in st.items() if k not in ("all_reduce", "update")),
                               "profiles/r06_train_rcnn_kernel_stats.csv (rocprofv3 --kernel-trace --stats of `bench.py --mode train-rcnn`)")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and params is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and params is not None:
             try:
                 cpu = cpu_train_baseline(params, x_host, gt.data, stage2=True, samples=3, warmups=1, rank_seed=rank)
             except Exception as e:
@@ -901,7 +948,7 @@ def main():
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the forward as ONE captured hipGraph in the timed region (auto = on: the ~45 launches of a bf16 step are "
                          "shorter than the host can issue them, and the f32 step, GPU-bound in eager mode on a quiet host, lost up to "
-                         "10 % of wall clock to host jitter on some boxes; off = eager launches)")
+                         "10 %% of wall clock to host jitter on some boxes; off = eager launches)")
     ap.add_argument("--dtype", choices=["f32", "f32s", "bf16", "f16"], default="f32",
                     help="f32 = BASELINE.json configs[1] (the contract line); bf16 = configs[2]: bf16 convolutions, fp32 RoI / head; f16 = the fp16 instantiation of the "
                          "same 16-bit chain (north_star: fp16/bf16 accumulate fp32): same kernels and rate, 10 mantissa bits")
@@ -911,6 +958,10 @@ def main():
                     help="--mode train-rcnn: where F.dropout's masks are drawn (numpy = the reference CPU path's random stream, on the host)")
     ap.add_argument("--mode", choices=["infer", "train", "train-rcnn"], default="infer",
                     help="infer = BASELINE.json configs[1] (the contract line); train = configs[4], the RPN training step; train-rcnn = the stage-2 step of train_rcnn.py (SURVEY 8f-2)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run every secondary measurement and check (stage events, roofline, isolated graphs, feed / two-in-flight forms, bf16 / f16 / split-product variants, CPU baseline, parity; training modes: CPU baseline, the step without ProposalLayer)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MiB)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = DEFAULT_STEPS if args.mode == "infer" else 40
@@ -973,7 +1024,7 @@ def main():
         torch.cuda.synchronize()
     for _ in range(args.warmup):
         model.forward_device(x, IM_H, IM_W)
-    timer = None if args.no_stage_events else EventTimer(torch)
+    timer = None if (args.no_stage_events or not args.full) else EventTimer(torch)
     if use_graph:
         # Stage events come from an eager pass (they cannot be read out of a replayed graph); the TIMED region below is
         # K replays of one captured hipGraph of the whole forward: no Python, no per-launch host cost inside it.
@@ -1010,9 +1061,11 @@ def main():
                 eager_timer.end()
         barrier()
         dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, inference_outputs(rt, out))
     n_rois = int(out["n_out"].cpu()[0])
     feed_main = None
-    if rank == 0 and world == 1 and use_graph and not args.no_feed_variant:
+    if args.full and rank == 0 and world == 1 and use_graph and not args.no_feed_variant:
         try:
             feed_main = feed_variant(torch, rt, graph, max(args.steps, 50), check_oracle=not args.no_cpu_baseline)
         except Exception as e:
@@ -1020,7 +1073,7 @@ def main():
             torch.cuda.synchronize()
         graph.replay(x)                                           # the resident image back in the graph's input (parity below reads its outputs)
     two_main = None
-    if rank == 0 and world == 1 and use_graph and not args.no_two_streams_variant:
+    if args.full and rank == 0 and world == 1 and use_graph and not args.no_two_streams_variant:
         try:
             graph.replay(x)
             torch.cuda.synchronize()
@@ -1032,7 +1085,7 @@ def main():
     # hipGraph, replays bracketed by HIP events on the launch stream -- kernel time only, whatever the host is doing
     conv_chain_ms, iso = None, {}
     iso_replays = max(args.steps, 100)
-    if rank == 0 and args.graph != "off" and not args.no_stage_events:
+    if args.full and rank == 0 and args.graph != "off" and not args.no_stage_events:
         try:
             if args.dtype == "f32":
                 def conv_chain():
@@ -1186,7 +1239,7 @@ def main():
         if two_main is not None:
             res["two_images_in_flight"] = two_main
         dbg = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"], dbg = cpu_baseline(params, x_host, args.cpu_samples)
             except Exception as e:                                 # the measured line is never lost to the checker's side (a missing oracle/_ref, a host without gcc ...)
@@ -1203,7 +1256,7 @@ def main():
                 res["parity"] = rep
             except Exception as e:
                 res["parity"] = {"ok": False, "error": repr(e)}
-        if world == 1 and args.dtype == "f32" and not args.no_bf16_variant:
+        if args.full and world == 1 and args.dtype == "f32" and not args.no_bf16_variant:
             try:
                 from chainer_faster_rcnn_amd.models.vgg16 import LAYERS as _L3
                 res["bf16_config3"] = bf16_variant(args, torch, rt, params, x, dbg, sum(conv_flops(_L3, IM_H, IM_W)[0].values()))
@@ -1214,7 +1267,7 @@ def main():
             except Exception as e:
                 res["f16_config3"] = {"error": repr(e)}
                 torch.cuda.synchronize()
-        if world == 1 and args.dtype == "f32" and not args.no_split_variant:
+        if args.full and world == 1 and args.dtype == "f32" and not args.no_split_variant:
             try:
                 from chainer_faster_rcnn_amd.models.vgg16 import LAYERS as _L
                 res["f32_split_products"] = split_variant(args, torch, rt, params, x, dbg, sum(conv_flops(_L, IM_H, IM_W)[0].values()))

@@ -16,30 +16,30 @@ if has tests; then
   grep -E "^PARITY|full-size weight" $O/pytest_gpu.log > $O/parity_reports.txt
 fi
 if has bench; then
-  echo "== bench f32 (contract line)"; T0=$(date +%s); timeout 900 python bench.py > $O/${P}_bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"; cut -c1-300 $O/${P}_bench.json
-  echo "== bench bf16"; timeout 600 python bench.py --dtype bf16 --steps 100 --warmup 5 > $O/${P}_bench_bf16.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_bf16.json
-  echo "== bench f32s"; timeout 600 python bench.py --dtype f32s --steps 100 --warmup 5 > $O/${P}_bench_f32s.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_f32s.json
-  echo "== bench train"; timeout 600 python bench.py --mode train --steps 40 --warmup 3 > $O/${P}_bench_train.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_train.json
-  echo "== bench train f32s"; timeout 600 python bench.py --mode train --dtype f32s --steps 40 --warmup 3 > $O/${P}_bench_train_f32s.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_train_f32s.json
+  echo "== bench f32 (contract line)"; T0=$(date +%s); timeout 900 python bench.py --full > $O/${P}_bench.json 2> $O/bench.err; echo "bench rc=$? wall $(( $(date +%s) - T0 )) s"; cut -c1-300 $O/${P}_bench.json
+  echo "== bench bf16"; timeout 600 python bench.py --full --dtype bf16 --steps 100 --warmup 5 > $O/${P}_bench_bf16.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_bf16.json
+  echo "== bench f32s"; timeout 600 python bench.py --full --dtype f32s --steps 100 --warmup 5 > $O/${P}_bench_f32s.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_f32s.json
+  echo "== bench train"; timeout 600 python bench.py --full --mode train --steps 40 --warmup 3 > $O/${P}_bench_train.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_train.json
+  echo "== bench train f32s"; timeout 600 python bench.py --full --mode train --dtype f32s --steps 40 --warmup 3 > $O/${P}_bench_train_f32s.json 2>> $O/bench.err; echo "rc=$?"; cut -c1-200 $O/${P}_bench_train_f32s.json
 fi
 if has dist; then
   echo "== RCCL world 1 / gloo 2 ranks"
-  timeout 400 python bench.py --mode train --dist-world1 --steps 40 > $O/${P}_bench_nccl_w1_train.json 2> $O/dist.err; echo "nccl w1 rc=$?"
-  FRCNN_COMM_TRACE=1 timeout 600 python bench.py --gpus 2 --mode train --steps 20 > $O/${P}_bench_2rank_gloo_train.json 2>> $O/dist.err; echo "gloo2 train rc=$?"
-  timeout 600 python bench.py --gpus 2 --steps 100 --no-cpu-baseline > $O/${P}_bench_2rank_gloo_infer.json 2>> $O/dist.err; echo "gloo2 infer rc=$?"
+  timeout 400 python bench.py --full --mode train --dist-world1 --steps 40 > $O/${P}_bench_nccl_w1_train.json 2> $O/dist.err; echo "nccl w1 rc=$?"
+  FRCNN_COMM_TRACE=1 timeout 600 python bench.py --full --gpus 2 --mode train --steps 20 > $O/${P}_bench_2rank_gloo_train.json 2>> $O/dist.err; echo "gloo2 train rc=$?"
+  timeout 600 python bench.py --full --gpus 2 --steps 100 --no-cpu-baseline > $O/${P}_bench_2rank_gloo_infer.json 2>> $O/dist.err; echo "gloo2 infer rc=$?"
 fi
 if has prof; then
   echo "== rocprof kernel stats"; cd /tmp && export TMPDIR=/tmp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o ${P} -- python "$R/bench.py" --steps 100 --warmup 5 --no-cpu-baseline --no-split-variant --no-bf16-variant --no-feed-variant --no-two-streams-variant > "$R/$O/prof.log" 2>&1; echo "rocprof f32 rc=$?"
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_bf16" -o ${P}_bf16 -- python "$R/bench.py" --dtype bf16 --steps 100 --warmup 5 --no-cpu-baseline --no-feed-variant --no-two-streams-variant > "$R/$O/prof_bf16.log" 2>&1; echo "rocprof bf16 rc=$?"
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_train" -o ${P}_train -- python "$R/bench.py" --mode train --steps 10 --warmup 2 > "$R/$O/prof_train.log" 2>&1; echo "rocprof train rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof" -o ${P} -- python "$R/bench.py" --full --steps 100 --warmup 5 --no-cpu-baseline --no-split-variant --no-bf16-variant --no-feed-variant --no-two-streams-variant > "$R/$O/prof.log" 2>&1; echo "rocprof f32 rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_bf16" -o ${P}_bf16 -- python "$R/bench.py" --full --dtype bf16 --steps 100 --warmup 5 --no-cpu-baseline --no-feed-variant --no-two-streams-variant > "$R/$O/prof_bf16.log" 2>&1; echo "rocprof bf16 rc=$?"
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$O/prof_train" -o ${P}_train -- python "$R/bench.py" --full --mode train --steps 10 --warmup 2 > "$R/$O/prof_train.log" 2>&1; echo "rocprof train rc=$?"
   cd "$R"
   for d in prof prof_bf16 prof_train; do find $O/$d -type f ! -name "*kernel_stats.csv" -delete 2>/dev/null; done       # keep the per-kernel statistics, drop the raw traces
 fi
 if has pmc; then
   echo "== hbm traffic PMC"; cd /tmp && export TMPDIR=/tmp
   for dt in f32 bf16; do for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/$O/traffic_${dt}_$c" -o t -- python "$R/bench.py" --dtype $dt --steps 3 --warmup 2 --no-cpu-baseline --no-split-variant --no-bf16-variant --no-feed-variant --no-two-streams-variant > "$R/$O/traffic_${dt}_$c.log" 2>&1; echo "$dt $c rc=$?"
+    timeout 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$R/$O/traffic_${dt}_$c" -o t -- python "$R/bench.py" --full --dtype $dt --steps 3 --warmup 2 --no-cpu-baseline --no-split-variant --no-bf16-variant --no-feed-variant --no-two-streams-variant > "$R/$O/traffic_${dt}_$c.log" 2>&1; echo "$dt $c rc=$?"
   done; done
   cd "$R"; for dt in f32 bf16; do python scripts/gpu_traffic.py $O $dt ${P} > $O/traffic_${dt}_summary.txt 2>&1; done; tail -8 $O/traffic_f32_summary.txt
   rm -rf $O/traffic_f32_FETCH_SIZE $O/traffic_f32_WRITE_SIZE $O/traffic_bf16_FETCH_SIZE $O/traffic_bf16_WRITE_SIZE        # raw counter csvs: tens of MB (gpurun copies back at most 64 MiB); the summaries stay

@@ -30,7 +30,7 @@ def main(out_dir, dtype):
         fl = [v for n, vs in acc["FETCH_SIZE"].items() if pred(n) for v in vs]
         wl = [v for n, vs in acc["WRITE_SIZE"].items() if pred(n) for v in vs]
         return len(fl), 1024.0 * sum(fl) / max(1, len(fl)), 1024.0 * sum(wl) / max(1, len(wl))
-    summ = {"command": "python bench.py --dtype %s --steps 3 --warmup 2 --no-cpu-baseline --no-stage-events (two passes: --pmc FETCH_SIZE, --pmc WRITE_SIZE, "
+    summ = {"command": "python bench.py --full --dtype %s --steps 3 --warmup 2 --no-cpu-baseline --no-stage-events (two passes: --pmc FETCH_SIZE, --pmc WRITE_SIZE, "
                        "--kernel-trace only)" % dtype}
     if dtype == "f32":
         n, fb, wb = family(lambda s: s.startswith("conv_mfma_f32_kernel<3"))

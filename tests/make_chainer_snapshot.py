@@ -55,6 +55,8 @@ def main():
         path = k[len("updater/model:main/"):]
         if path.startswith("trunk/") or path.startswith("RPN/"):                      # rpn_train mode: only trunk + RPN have optimizer state
             tr["updater/optimizer:main/" + path + "/v"] = (rs.randn(*v.shape) * 1e-3).astype(np.float32)
+    # float32 values on the float16 grid (13 low mantissa bits zero): the file then compresses to well under 1 MiB
+    tr = {k: v.astype(np.float16).astype(np.float32) for k, v in tr.items()}
     tr["updater/optimizer:main/t"] = np.asarray(37, dtype=np.int32)
     tr["updater/optimizer:main/epoch"] = np.asarray(0, dtype=np.int32)
     tr["updater/iteration"] = np.asarray(37, dtype=np.int32)

@@ -256,10 +256,45 @@ def proposal_target_cases(ns):
     np.savez_compressed(os.path.join(OUT, "proposal_target.npz"), **out)
 
 
+SWEEP_SEEDS = (0, 1, 2)
+SWEEP_NMS_THRESHOLDS = (0.3, 0.5, 0.7)
+
+
+def random_sweep_case(seed):
+    """Inputs of tests/test_oracle_pinned.py::test_live_reference_random_sweep for one seed: ProposalLayer maps (tie-free scores, random
+    deltas) of a random size, and 500 random boxes with distinct scores for cpu_nms."""
+    rs = np.random.RandomState(100 + seed)
+    fh, fw = rs.randint(8, 30), rs.randint(8, 40)
+    prob = rs.permutation(18 * fh * fw).reshape(1, 18, fh, fw).astype(np.float32) / (18 * fh * fw)
+    pred = (rs.randn(1, 36, fh, fw) * 0.3).astype(np.float32)
+    info = np.array([[fh * 16, fw * 16]], np.int32)
+    n = 500
+    x1 = rs.uniform(0, 300, n); y1 = rs.uniform(0, 300, n)
+    dets = np.stack([x1, y1, x1 + rs.uniform(1, 200, n), y1 + rs.uniform(1, 200, n),
+                     rs.permutation(n) / float(n)], 1).astype(np.float32)
+    return prob, pred, info, dets
+
+
+def random_sweep(ns):
+    """The reference's ProposalLayer (train mode on odd seeds) and cpu_nms on random_sweep_case's inputs."""
+    out = {}
+    for seed in SWEEP_SEEDS:
+        prob, pred, info, dets = random_sweep_case(seed)
+        pl = ns.ProposalLayer()
+        pl.train = bool(seed % 2)
+        out["s%d_proposals" % seed], out["s%d_scores" % seed] = pl(ns.Variable(prob.copy()), ns.Variable(pred.copy()), ns.Variable(info))
+        for thr in SWEEP_NMS_THRESHOLDS:
+            out["s%d_keep_%g" % (seed, thr)] = np.array(ns.cpu_nms(dets, thr), np.int64)
+    np.savez_compressed(os.path.join(OUT, "random_sweep.npz"), **out)
+
+
 if __name__ == "__main__":
     if "--edges" in sys.argv:          # only the edge fixture (the others regenerate identically; this avoids the churn)
         edge_cases(rh.load())
+    elif "--sweep" in sys.argv:        # only the random-sweep fixture
+        random_sweep(rh.load())
     else:
         main()
         proposal_target_cases(rh.load())
         edge_cases(rh.load())
+        random_sweep(rh.load())

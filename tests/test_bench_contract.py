@@ -1,10 +1,12 @@
-"""bench.py pieces that do not need a GPU: the algorithmic work the roofline is priced on, and the loud failure without a device."""
+"""bench.py pieces that do not need a GPU: the algorithmic work the roofline is priced on, the loud failure without a device, the
+--full / --dump-outputs options; and (marked gpu) what a plain run prints and dumps."""
 import importlib.util
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,3 +112,58 @@ def test_every_baseline_config_line_carries_roofline_and_cpu_baseline():
         r, c = line["roofline"], line["cpu_baseline"]
         assert r["bound"] == "mfma" and r["peak"] == 157.3 and 0.2 < r["frac"] < 1.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9, name
         assert c["unit"] == "img/s" and c["value"] > 0 and c["cores"] >= 1 and c["kind"] in ("reference-native", "port") and c[key] > 100 and "sample" in c, name
+
+
+def test_full_and_dump_outputs_options():
+    """`--full` (every secondary measurement) and `--dump-outputs DIR` are options of the benchmark; --help works without a GPU."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import torch
+    b = _bench()
+    out = {"cls_prob": np.ones((300, 21), np.float32), "rois": np.zeros((300, 4), np.float32), "n_out": np.array([7], np.int32),
+           "probs": np.ones(300, np.float32)}
+    res = b.inference_outputs(type("R", (), {"mem": type("M", (), {"to_numpy": staticmethod(np.asarray)})()})(),
+                              dict(out, pred_boxes=np.ones((300, 84), np.float32)))
+    assert [res[k].shape[0] for k in ("cls_prob", "pred_boxes", "rois", "probs")] == [7] * 4 and res["n_out"].tolist() == [7.0]
+    names = b.dump_outputs(str(tmp_path / "d"), res)
+    assert names == ["cls_prob", "n_out", "pred_boxes", "probs", "rois"]
+    for n in names:
+        a = np.load(str(tmp_path / "d" / (n + ".npy")))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, res[n])
+    with pytest.raises(ValueError):
+        b.dump_outputs(str(tmp_path / "big"), {"w": np.zeros(b.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    # a large flat buffer: the same seeded sample every time, at most DUMP_SAMPLE elements
+    flat = torch.arange(3 * b.DUMP_SAMPLE, dtype=torch.float32)
+    s1, s2 = b.flat_sample(torch, flat), b.flat_sample(torch, flat)
+    assert np.array_equal(s1, s2) and 0.5 * b.DUMP_SAMPLE < len(s1) <= b.DUMP_SAMPLE and np.all(np.diff(s1) > 0)
+    assert np.array_equal(b.flat_sample(torch, flat[:100]), np.arange(100, dtype=np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_forward(tmp_path):
+    """A plain run: the line carries the contract fields and `steps` = --steps, none of the --full blocks; --dump-outputs holds the
+    forward's valid rows, equal to an eager forward of the same seeded image and weights."""
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"] and line["unit"] == "img/s"
+    assert not {"roofline", "cpu_baseline", "parity", "bf16_config3", "f32_split_products", "with_feed", "stages_ms"} & set(line)
+    import chainer_faster_rcnn_amd as pkg
+    from chainer_faster_rcnn_amd import synthetic
+    from chainer_faster_rcnn_amd.models import FasterRCNN
+    b = _bench()
+    rt = pkg.runtime.default_runtime()
+    model = FasterRCNN(runtime=rt)
+    model.load_params(synthetic.params(seed=1))
+    want = b.inference_outputs(rt, model.forward_device(rt.mem.from_numpy(synthetic.image(seed=0, h=b.IM_H, w=b.IM_W)), b.IM_H, b.IM_W))
+    assert sorted(p.name for p in d.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        got = np.load(str(d / (k + ".npy")))
+        assert got.dtype in (np.float32, np.float64) and got.shape == v.shape, k
+        assert np.allclose(got, v, rtol=1e-5, atol=1e-5), k

@@ -187,27 +187,25 @@ def test_roi_bin_edges_need_double_arithmetic():
     assert bad > 0
 
 
-@pytest.mark.skipif(not rh.available(), reason="reference tree not present (GPU box)")
-def test_live_reference_random_sweep():
-    """Beyond the committed fixtures: fresh seeds, oracle vs the reference executed right now."""
-    ns = rh.load()
-    for seed in range(3):
-        rs = np.random.RandomState(100 + seed)
-        fh, fw = rs.randint(8, 30), rs.randint(8, 40)
-        prob = rs.permutation(18 * fh * fw).reshape(1, 18, fh, fw).astype(np.float32) / (18 * fh * fw)
-        pred = (rs.randn(1, 36, fh, fw) * 0.3).astype(np.float32)
-        info = np.array([[fh * 16, fw * 16]], np.int32)
-        pl = ns.ProposalLayer()
-        pl.train = bool(seed % 2)
-        rp, rsn = pl(ns.Variable(prob.copy()), ns.Variable(pred.copy()), ns.Variable(info))
+def test_live_reference_random_sweep(golden):
+    """Beyond the committed fixtures: random seeds, oracle vs the reference -- its outputs recorded by tests/make_golden.py
+    (golden/random_sweep.npz) and, where the reference tree is present, the reference executed right now."""
+    from make_golden import SWEEP_NMS_THRESHOLDS, SWEEP_SEEDS, random_sweep_case
+    g = golden("random_sweep")
+    ns = rh.load() if rh.available() else None
+    for seed in SWEEP_SEEDS:
+        prob, pred, info, d = random_sweep_case(seed)
         op, osn = O.proposal_layer(prob, pred, info, train=bool(seed % 2))
-        assert np.array_equal(rp, op) and np.array_equal(rsn, osn)
-        n = 500
-        x1 = rs.uniform(0, 300, n); y1 = rs.uniform(0, 300, n)
-        d = np.stack([x1, y1, x1 + rs.uniform(1, 200, n), y1 + rs.uniform(1, 200, n),
-                      rs.permutation(n) / float(n)], 1).astype(np.float32)
-        for thr in (0.3, 0.5, 0.7):
-            assert ns.cpu_nms(d, thr) == O.cpu_nms(d, thr)
+        assert np.array_equal(g["s%d_proposals" % seed], op) and np.array_equal(g["s%d_scores" % seed], osn)
+        for thr in SWEEP_NMS_THRESHOLDS:
+            assert O.cpu_nms(d, thr) == g["s%d_keep_%g" % (seed, thr)].tolist()
+        if ns is not None:
+            pl = ns.ProposalLayer()
+            pl.train = bool(seed % 2)
+            rp, rsn = pl(ns.Variable(prob.copy()), ns.Variable(pred.copy()), ns.Variable(info))
+            assert np.array_equal(rp, op) and np.array_equal(rsn, osn)
+            for thr in SWEEP_NMS_THRESHOLDS:
+                assert ns.cpu_nms(d, thr) == O.cpu_nms(d, thr)
 
 
 def test_ref_native_so_travels():
