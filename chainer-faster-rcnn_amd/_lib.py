@@ -119,6 +119,18 @@ SIGNATURES = {
     "frcnn_linear_f16_tiled": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_im2col7x7s2_f32": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "frcnn_maxpool3x3s2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "frcnn_conv1x1_bf16_workspace_bytes": (_S, [_I, _I, _I, _I, _I]),
+    "frcnn_conv1x1_bf16_workspace_init": (_I, [_P, _S, _P]),
+    "frcnn_conv1x1_bf16_splits": (_I, [_I, _I, _I, _I, _I]),
+    "frcnn_conv1x1_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_im2col7x7s2_bf16": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "frcnn_maxpool3x3s2_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
+    "frcnn_conv1x1_f16_workspace_bytes": (_S, [_I, _I, _I, _I, _I]),
+    "frcnn_conv1x1_f16_workspace_init": (_I, [_P, _S, _P]),
+    "frcnn_conv1x1_f16_splits": (_I, [_I, _I, _I, _I, _I]),
+    "frcnn_conv1x1_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_im2col7x7s2_f16": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "frcnn_maxpool3x3s2_f16": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_subsample2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_bbox_overlaps_f64": (_I, [_P, _I, _P, _I, _P, _P]),
     "frcnn_anchor_target_workspace_bytes": (_S, [_I, _I, _I, _I]),

@@ -790,6 +790,44 @@ class Runtime(object):
         _lib.check(L.frcnn_subsample2_f32(m.ptr(x), m.ptr(y), C, H, W, m.stream()), "frcnn_subsample2_f32")
         return y
 
+    # the same pieces on the 16-bit chain (csrc/resnet_bf16.hip; through self.hlib, so with_half("f16") runs the fp16 twins)
+    def conv1x1_bf16(self, x, w_packed, bias, cin, cout, stride=1, act=1, residual=None):
+        """x [CinP/16][H][W][16] -> [CoutP/16][Ho][Wo][16] (Ho = ceil(H/stride)): act 0 none, 1 ReLU, 3 relu(conv + b + residual)."""
+        m, L = self.mem, self.hlib
+        H, W = int(x.shape[1]), int(x.shape[2])
+        assert int(x.shape[0]) * 16 == self.bf16_pad(cin) and int(w_packed.shape[0]) * 16 == self.bf16_pad(cin) and stride in (1, 2)
+        Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
+        y = m.empty((self.bf16_pad(cout) // 16, Ho, Wo, 16), "i16")
+        if act == 3:
+            assert residual is not None and tuple(int(v) for v in residual.shape) == tuple(int(v) for v in y.shape)
+        ws = self.workspace("conv1x1_bf16", L.frcnn_conv1x1_bf16_workspace_bytes(int(cin), int(cout), H, W, int(stride)),
+                            init=lambda w: _lib.check(L.frcnn_conv1x1_bf16_workspace_init(m.ptr(w), w.shape[0], m.stream()),
+                                                      "frcnn_conv1x1_bf16_workspace_init"))
+        _lib.check(L.frcnn_conv1x1_bf16(m.ptr(x), m.ptr(w_packed), m.ptr(bias), m.ptr(residual) if residual is not None else None, m.ptr(y),
+                                        int(cin), int(cout), H, W, int(stride), int(act), m.ptr(ws), ws.shape[0], m.stream()), "frcnn_conv1x1_bf16")
+        return y
+
+    def conv1x1_bf16_splits(self, cin, cout, H, W, stride=1):
+        """the K split frcnn_conv1x1_bf16 takes for this shape (with a large enough workspace)"""
+        return self.hlib.frcnn_conv1x1_bf16_splits(int(cin), int(cout), int(H), int(W), int(stride))
+
+    def im2col7x7s2_bf16(self, x, Kp):
+        """fp32 NCHW image -> the stem's columns, blocked [Kp/16][Ho][Wo][16] (rows past Cin*49 zero)."""
+        m, L = self.mem, self.hlib
+        C, H, W = [int(v) for v in x.shape[-3:]]
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        cols = m.empty((int(Kp) // 16, OH, OW, 16), "i16")
+        _lib.check(L.frcnn_im2col7x7s2_bf16(m.ptr(x), C, H, W, int(Kp), m.ptr(cols), m.stream()), "frcnn_im2col7x7s2_bf16")
+        return cols
+
+    def maxpool3x3s2_bf16(self, x):
+        """F.max_pooling_2d(3, stride=2), cover_all, on a blocked map [CP/16][H][W][16]."""
+        m, L = self.mem, self.hlib
+        CB, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        y = m.empty((CB, (H - 2) // 2 + 1, (W - 2) // 2 + 1, 16), "i16")
+        _lib.check(L.frcnn_maxpool3x3s2_bf16(m.ptr(x), m.ptr(y), CB * 16, H, W, m.stream()), "frcnn_maxpool3x3s2_bf16")
+        return y
+
     def bbox_overlaps(self, boxes, query_boxes):
         m, L = self.mem, self.lib
         N, K = int(boxes.shape[0]), int(query_boxes.shape[0])

@@ -429,6 +429,33 @@ int frcnn_softmax_channels_f32(const float *score, int n_ch, int HW, float *prob
 int frcnn_im2col7x7s2_f32(const float *x, int Cin, int H, int W, int Kp, float *cols, void *stream);
 int frcnn_maxpool3x3s2_f32(const float *x, float *y, int C, int H, int W, void *stream);
 int frcnn_subsample2_f32(const float *x, float *y, int C, int H, int W, void *stream);
+/* The same trunk pieces on the 16-bit chain (csrc/resnet_bf16.hip; fp16 twins below) -- /root/reference/models/resnet.py:11-45 -> chainer ResNetLayers
+ * (conv1 7x7/2 + bn1 + relu, pool1 3x3/2, the res2..res5 bottlenecks' 1x1 convolutions with BatchNormalization folded in).  Maps are channel-blocked
+ * [CP/16][H][W][16] 16-bit, CP = frcnn_bf16_padded_channels(C); weights frcnn_bf16_pack_conv_w(..., ksize 1) of the folded (Cout, Cin) matrix.
+ * frcnn_conv1x1_bf16: y[co][p] = act(sum_ci W[co][ci] x[ci][src(p)] + b[co] (+ residual[co][p])), a GEMM over the flat pixel axis; stride 1, or 2
+ *   (Ho = ceil(H/2), Wo = ceil(W/2), src = (2y, 2x): Chainer's 1x1 / stride 2 / pad 0, replaces frcnn_subsample2_f32 + the 1x1); act 0 = none
+ *   (projection shortcut conv4), 1 = ReLU (conv1), 3 = relu(conv + b + residual) (the bottleneck tail conv3; residual = a blocked map of y's shape).
+ *   Launches with fewer tiles than CUs split K across workgroups through `workspace` (frcnn_conv1x1_bf16_workspace_bytes for the shape; its first
+ *   64 KB are tile counters: zero them once with frcnn_conv1x1_bf16_workspace_init, every launch leaves them zeroed; one workspace per stream; partial
+ *   tiles are summed in split order, deterministic).  workspace NULL (or too small) = no split.  frcnn_conv1x1_bf16_splits: the split the launch takes.
+ * frcnn_im2col7x7s2_bf16: the stem's columns from the fp32 NCHW image, written blocked [Kp/16][Ho][Wo][16] (Kp % 16 == 0, Kp >= Cin*49, rows past
+ *   Cin*49 zero); the stem then runs as frcnn_conv1x1_bf16 with Cin = Kp.  Replaces frcnn_im2col7x7s2_f32.
+ * frcnn_maxpool3x3s2_bf16: F.max_pooling_2d(3, stride=2), cover_all, blocked in and out; exactly frcnn_maxpool3x3s2_f32 on the widened map. */
+size_t frcnn_conv1x1_bf16_workspace_bytes(int Cin, int Cout, int H, int W, int stride);
+int frcnn_conv1x1_bf16_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_conv1x1_bf16_splits(int Cin, int Cout, int H, int W, int stride);
+int frcnn_conv1x1_bf16(const uint16_t *x, const uint16_t *w_packed, const float *bias, const uint16_t *residual, uint16_t *y, int Cin, int Cout,
+                       int H, int W, int stride, int act, void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_im2col7x7s2_bf16(const float *x, int Cin, int H, int W, int Kp, uint16_t *cols, void *stream);
+int frcnn_maxpool3x3s2_bf16(const uint16_t *x, uint16_t *y, int C, int H, int W, void *stream);
+/* their fp16 twins (csrc/resnet_f16.hip: the same source under FRCNN_HALF_F16; same signatures, layouts and workspace contract) */
+size_t frcnn_conv1x1_f16_workspace_bytes(int Cin, int Cout, int H, int W, int stride);
+int frcnn_conv1x1_f16_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_conv1x1_f16_splits(int Cin, int Cout, int H, int W, int stride);
+int frcnn_conv1x1_f16(const uint16_t *x, const uint16_t *w_packed, const float *bias, const uint16_t *residual, uint16_t *y, int Cin, int Cout,
+                      int H, int W, int stride, int act, void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_im2col7x7s2_f16(const float *x, int Cin, int H, int W, int Kp, uint16_t *cols, void *stream);
+int frcnn_maxpool3x3s2_f16(const uint16_t *x, uint16_t *y, int C, int H, int W, void *stream);
 
 /* ---- RPN training step --------------------------------------------------------
  * frcnn_bbox_overlaps_f64: bbox_overlaps(boxes (N,4) f64, query_boxes (K,4) f64) -> (N,K) f64   (models/bbox.pyx:16-56)

@@ -4,7 +4,8 @@
 whole-forward hipGraph replay time, the trunk alone as its own hipGraph (HIP events on the launch stream) priced against the fp32
 MFMA peak with the trunk's algorithmic FLOPs, per-stage HIP events of eager forwards (fc6 = 300 x 100352 x 4096 called out), and the
 comparison of res5 / proposals with nothing (parity lives in tests/test_gpu_fullsize.py::test_resnet101_config4_600x1000).
-GPU only.  Usage: python scripts/resnet_bench.py [> profiles/r03_bench_resnet101.json]"""
+GPU only.  Usage: python scripts/resnet_bench.py [--dtype f32|bf16|f16] [> profiles/r03_bench_resnet101.json]
+(--dtype bf16 / f16: the 16-bit network, trunk priced against the dense 16-bit peak, with its launch count and a `parity` object.)"""
 import json
 import os
 import sys
@@ -87,7 +88,115 @@ def cpu_baseline_resnet(params, x, samples=3, warmups=1):
             "ms_per_image": med * 1e3, "stages_ms": {k: round(float(np.median(v)), 2) for k, v in stages.items()}}
 
 
+class _LaunchCounter(object):
+    """the runtime's 16-bit library seen through a counter of the entry points that launch a kernel (sizes / plans / workspace queries excluded)"""
+
+    def __init__(self, lib):
+        self._lib, self.n = lib, 0
+
+    def __getattr__(self, name):
+        f = getattr(self._lib, name)
+        if any(t in name for t in ("_workspace_bytes", "_splits", "_plan", "_padded_channels", "_workspace_init")):
+            return f
+
+        def call(*a):
+            self.n += 1
+            return f(*a)
+        return call
+
+
+def main_16bit(dtype):
+    """--dtype bf16 | f16: the same network with conv_dtype = head_dtype = dtype (csrc/resnet_bf16.hip for the trunk's 1x1 / stem / pool, the 16-bit
+    3x3 kernels, RPN heads, RoI pooling from the blocked map and FC head).  Trunk graph time priced against the dense 16-bit peak, per-stage HIP
+    events, the trunk's launch count, parity of res5 and of the proposals against the oracle."""
+    from oracle import frcnn_oracle as O
+    rt = pkg.runtime.default_runtime()
+    h, w = 600, 1000
+    params = synthetic.resnet_params(101, seed=2)
+    rs = np.random.RandomState(3)
+    head = synthetic.params(seed=1, rpn_ch=512, roi_feat=2048 * 49)
+    for k in ("fc6", "fc7", "cls_score", "bbox_pred"):
+        params[k + "/W"], params[k + "/b"] = head[k + "/W"], head[k + "/b"]
+    params["RPN/rpn_conv_3x3/W"] = (rs.randn(512, 2048, 3, 3) * 0.01).astype(np.float32)
+    params["RPN/rpn_conv_3x3/b"] = np.zeros(512, np.float32)
+    for k in ("rpn_cls_score", "rpn_bbox_pred"):
+        params["RPN/%s/W" % k], params["RPN/%s/b" % k] = head["RPN/%s/W" % k], head["RPN/%s/b" % k]
+    model = FasterRCNN(trunk_class=ResNet101, rpn_in_ch=2048, rpn_mid_ch=512, feat_stride=32, runtime=rt, conv_dtype=dtype, head_dtype=dtype)
+    model.load_params(params)
+    model.RPN.proposal_layer._pre_nms_top_n, model.RPN.proposal_layer._post_nms_top_n = 1000, 300
+    x_host = synthetic.image(seed=6, h=h, w=w) / 64.0
+    x = rt.mem.from_numpy(x_host)
+    t_ramp = time.perf_counter()
+    while time.perf_counter() - t_ramp < 1.0:                                          # clock ramp, untimed
+        model.forward_device(x, h, w)
+        torch.cuda.synchronize()
+    timer = bench.EventTimer(torch)
+    for _ in range(10):
+        timer.begin()
+        model.forward_device(x, h, w, timer=timer)
+        timer.end()
+    torch.cuda.synchronize()
+    stages = timer.averages_ms()
+    trunk = model.trunk
+    trunk.skip_nchw = True                                                             # what forward_device runs: res5 stays blocked
+    try:
+        trunk_ms = bench.graph_time_us(torch, lambda: trunk(x), 1, 100) / 1e3
+        counter = _LaunchCounter(trunk.rt.hlib)
+        trunk.rt.hlib = counter
+        try:
+            trunk(x)
+        finally:
+            trunk.rt.hlib = counter._lib
+    finally:
+        trunk.skip_nchw = False
+    torch.cuda.synchronize()
+    cap = CapturedForward(model, x, h, w)
+    for _ in range(5):
+        cap.replay()
+    torch.cuda.synchronize()
+    steps = 100
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        out = cap.replay()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / steps * 1e3
+    # parity: res5 against the fp32 oracle; proposals (indices) given the device's own RPN maps
+    outk = model.forward_device(x, h, w, keep=True)
+    feat = rt.mem.to_numpy(outk["feat"])
+    want = O.resnet_forward(params, x_host)
+    info = np.array([[h, w]], dtype=np.int32)
+    n = int(rt.mem.to_numpy(outk["n_out"])[0])
+    p2, _, d2 = O.proposal_layer(rt.mem.to_numpy(outk["rpn_cls_prob"]), rt.mem.to_numpy(outk["rpn_bbox_pred"]), info, train=False, feat_stride=32,
+                                 pre_nms_top_n=1000, post_nms_top_n=300, return_debug=True)
+    parity = {"res5_rel_err_vs_fp32_oracle": float(np.abs(feat - want).max() / np.abs(want).max()),
+              "proposals_index_exact_given_device_maps": bool(n == len(p2) and np.array_equal(rt.mem.to_numpy(outk["src_index"])[:n],
+                                                                                              d2["src_index"].astype(np.int32))),
+              "n_rois": n}
+    per, (fh, fw) = resnet_trunk_flops(h, w)
+    trunk_flops = sum(per.values())
+    peak = 2500.0                                                                      # dense bf16 / fp16 MFMA peak of the MI355X, TFLOP/s
+    rec = {"metric": "images/sec ResNet-101 Faster R-CNN 600x1000", "value": 1e3 / ms, "unit": "img/s", "n_gpus": 1, "steps": steps, "warmup": 5,
+           "ms_per_step": ms, "higher_is_better": True, "dtype": dtype, "data": "synthetic",
+           "config": {"workload": "ResNet-101 backbone inference, 1xMI355X, batch 1, 1000 pre-NMS / 300 post-NMS proposals, conv_dtype = head_dtype = %s"
+                                  % dtype, "image": "1x3x600x1000", "launch": "hipGraph replay", "n_rois_last_step": int(out["n_out"].cpu()[0]),
+                      "feature_map": [2048, fh, fw]},
+           "roofline": {"bound": "launch count / occupancy", "kernel": "conv1x1_bf16_kernel (csrc/resnet_bf16.hip) for the stem and every 1x1, "
+                                                                         "frcnn_conv_bf16_ws for the 3x3s, maxpool3x3s2_bf16_kernel",
+                        "achieved": trunk_flops / (trunk_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
+                        "frac": trunk_flops / (trunk_ms * 1e-3) / 1e12 / peak, "trunk_ms": trunk_ms, "trunk_launches": counter.n,
+                        "trunk_ms_source": "HIP events around 100 replays of a hipGraph holding exactly the trunk's launches",
+                        "algorithmic_gflop_trunk": trunk_flops / 1e9},
+           "stages_ms": {k: round(v, 4) for k, v in stages.items()}, "parity": parity}
+    bench.emit_json_line(rec)
+
+
 def main():
+    if "--dtype" in sys.argv:
+        dtype = sys.argv[sys.argv.index("--dtype") + 1]
+        if dtype not in ("f32", "bf16", "f16"):
+            raise SystemExit("--dtype f32 | bf16 | f16")
+        if dtype != "f32":
+            return main_16bit(dtype)
     rt = pkg.runtime.default_runtime()
     h, w = 600, 1000
     params = synthetic.resnet_params(101, seed=2)
