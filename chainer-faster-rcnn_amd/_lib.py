@@ -42,6 +42,9 @@ SIGNATURES = {
     "frcnn_conv3x3_workspace_init": (_I, [_P, _S, _P]),
     "frcnn_conv3x3_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_conv3x3_f32_cfg": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_wino_pack_w": (_I, [_P, _I, _I, _I, _P, _P]),
+    "frcnn_conv_wino_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "frcnn_conv3x3_wino_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_maxpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_rpn_heads_padded_channels": (_I, [_I]),
     "frcnn_rpn_heads_pack": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),

@@ -152,6 +152,9 @@ class FasterRCNN(object):
         layout first)."""
         self._head_dirty = True
         self._derived_dirty = True
+        for link in list(getattr(self.trunk, "links", {}).values()) + [getattr(self.RPN, "rpn_conv_3x3", None)]:
+            if getattr(link, "Wu", None) is not None:
+                link.wu_stale = True                         # the Winograd weights: rebuilt from the packed ones at their next use
         if trainer is not None:
             # EVERY trainer that has updated this model holds live packed weights for its own parameter set (after an rpn -> rcnn
             # alternation the RPNTrainer still owns rpn_conv_3x3 and the RPN heads, the RCNNTrainer the trunk and the FC head):

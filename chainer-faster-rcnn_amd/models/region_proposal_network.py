@@ -74,7 +74,7 @@ class RegionProposalNetwork(object):
         if gt_boxes is not None:
             assert gt_boxes.shape[0] == 1 and gt_boxes.shape[2] == 5 and kind(gt_boxes) == 'f'
 
-    def heads(self, x, want_score=True, timer=None, x_bf16=None, x_split=None):
+    def heads(self, x, want_score=True, timer=None, x_bf16=None, x_split=None, wino=True):
         """(h, rpn_cls_score, rpn_cls_prob, rpn_bbox_pred) -- region_proposal_network.py:117-120.  x_bf16: the same map as the
         channel-blocked bf16 array the bf16 trunk produced (skips re-converting the fp32 copy)."""
         if self.conv_dtype == "bf16":
@@ -83,7 +83,8 @@ class RegionProposalNetwork(object):
             xs = x_split if x_split is not None else self.rt.f32s_from_nchw(self.rt.asarray(unwrap(x), "f32"))
             h = self.rpn_conv_3x3.f32s(xs, relu=True, out_f32_nchw=True)
         else:
-            h = self.rpn_conv_3x3(self.rt.asarray(unwrap(x), "f32"), relu=True)
+            conv = self.rpn_conv_3x3
+            h = conv.wino(self.rt.asarray(unwrap(x), "f32")) if wino and conv.wino_applies() else conv(self.rt.asarray(unwrap(x), "f32"), relu=True)
         if timer:
             timer.mark("rpn_conv_3x3")
         score, prob, bbox = self.rt.rpn_heads(h, self._heads_packed)

@@ -21,7 +21,7 @@ class Conv3x3(object):
 
     def __init__(self, rt, cin, cout, conv_dtype="f32"):
         self.rt, self.cin, self.cout, self.conv_dtype = rt, cin, cout, conv_dtype
-        self.W = self.b = self.Wp = self.Wb = self.Ws = None
+        self.W = self.b = self.Wp = self.Wb = self.Ws = self.Wu = None
 
     def set(self, W, b):
         rt = self.rt
@@ -36,6 +36,10 @@ class Conv3x3(object):
         else:
             self.Wp, self.b = Wp, b
         self.refresh_bf16()
+        # the Winograd weights of the fp32 inference forward (16 floats per (cout, cin) pair next to the 9 of Wp); made here, never during
+        # a forward (which may be under graph capture)
+        self.Wu = rt.pack_wino_w(self.W) if self.conv_dtype == "f32" and self.cin > 3 and self.cout % 64 == 0 else None
+        self.wu_stale = False
 
     def refresh_bf16(self):
         if self.conv_dtype == "bf16":
@@ -45,6 +49,20 @@ class Conv3x3(object):
 
     def __call__(self, x, relu=True, out=None, cfg=-1):
         return self.rt.conv3x3(x, self.Wp, self.b, relu=relu, out=out, cfg=cfg)
+
+    def wino_applies(self):
+        """The Winograd form serves the fp32 inference forward (the training steps keep the direct kernels): not conv1_1 (3 input
+        channels), and not with FRCNN_CONV_WINO=0 (the direct kernel, for A/B measurements)."""
+        return self.Wu is not None and _tuning.get("FRCNN_CONV_WINO", "1") != "0"
+
+    def wino(self, x, relu=True, pool=False):
+        """conv (+ ReLU) (+ the following F.MaxPooling2D(2,2)) as Winograd F(2x2,3x3) in fp32 (csrc/conv_wino.hip).  After an optimizer
+        update (wu_stale, set by FasterRCNN.mark_params_updated) U is first rebuilt in place from the live packed weights Wp."""
+        assert relu or not pool
+        if self.wu_stale:
+            self.rt.pack_wino_w(self.Wp, out=self.Wu)
+            self.wu_stale = False
+        return self.rt.conv3x3_wino(x, self.Wu, self.b, act=4 if pool else (1 if relu else 0))
 
     def relu_pool(self, x):
         """conv + ReLU + the following F.MaxPooling2D(2,2) in one launch (the pool lives in the conv kernel's epilogue)."""
@@ -108,7 +126,11 @@ class VGG16Prev(object):
                     collect["pool%d" % n_pool] = h
             else:
                 fuse = self.fuse_pool and idx + 1 < len(self.layers) and self.layers[idx + 1] == "pool" and l[2] % 64 == 0
-                h = self.links[l[0]].relu_pool(h) if fuse else self.links[l[0]](h, relu=True)
+                link = self.links[l[0]]
+                if link.wino_applies():
+                    h = link.wino(h, relu=True, pool=fuse)
+                else:
+                    h = link.relu_pool(h) if fuse else link(h, relu=True)
                 skip = fuse
                 if timer:
                     timer.mark(l[0])

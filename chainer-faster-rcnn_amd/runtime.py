@@ -504,6 +504,31 @@ class Runtime(object):
         return out
 
 
+    # ------------------------------------------------------------------ Winograd F(2x2,3x3) fp32 convolution (csrc/conv_wino.hip; inference only)
+    def pack_wino_w(self, w, out=None):
+        """(co, ci, 3, 3), or the packed (ci * 9, co) weights of pack_conv3x3_w -> U = G g G^T as (ci * 16, co) f32 ([ci][4][co][4]
+        underneath).  `out`: rewrite an existing U in place (no allocation)."""
+        m, L = self.mem, self.lib
+        packed = w.ndim == 2
+        co, ci = (int(w.shape[1]), int(w.shape[0]) // 9) if packed else (int(w.shape[0]), int(w.shape[1]))
+        u = out if out is not None else m.empty((ci * 16, co), "f32")
+        assert tuple(u.shape) == (ci * 16, co)
+        _lib.check(L.frcnn_wino_pack_w(m.ptr(w), co, ci, int(packed), m.ptr(u), m.stream()), "frcnn_wino_pack_w")
+        return u
+
+    def conv3x3_wino(self, x, u, bias, act=1, out=None):
+        """act 0 = + b, 1 = + b + ReLU, 4 = + b + ReLU + 2x2/2 ceil-mode max-pool."""
+        m, L = self.mem, self.lib
+        ci, H, W = [int(v) for v in x.shape[-3:]]
+        co = int(u.shape[1])
+        assert int(u.shape[0]) == ci * 16
+        oh, ow = ((H + 1) // 2, (W + 1) // 2) if act == 4 else (H, W)
+        y = out if out is not None else m.empty((1, co, oh, ow), "f32")
+        ws = self.workspace("conv_wino", L.frcnn_conv_wino_workspace_bytes(ci, co, H, W))
+        _lib.check(L.frcnn_conv3x3_wino_f32(m.ptr(x), m.ptr(u), m.ptr(bias), m.ptr(y), ci, co, H, W, int(act), m.ptr(ws), ws.shape[0],
+                                            m.stream()), "frcnn_conv3x3_wino_f32")
+        return y
+
     # ------------------------------------------------------------------ training step (csrc/train.hip)
     def conv_ex(self, x, w_packed, bias, ksize=3, act=1, mask=None, out=None):
         """Generic conv entry: act 0 none / 1 ReLU / 2 masked by (mask > 0) (the input-gradient convolution)."""

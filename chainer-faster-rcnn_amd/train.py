@@ -610,7 +610,7 @@ class RCNNTrainer(_BucketedAllReduce):
             feat, inputs = trunk_forward(model, x, fuse_pools=getattr(self, "keep_dy", None) is None)
         C, H, W = [int(v) for v in feat.shape[1:]]
         stage("trunk_fwd")
-        _, _, prob, bbox = model.RPN.heads(feat, want_score=False)
+        _, _, prob, bbox = model.RPN.heads(feat, want_score=False, wino=False)      # the training step keeps the direct convolution
         rois, _, n_out = model.RPN.proposal_layer.forward_device(prob, bbox, im_h, im_w)      # RPN.train is False in rcnn_train mode
         # ProposalTargetLayer needs the RoIs and the gt boxes only: its float64 IoU matrix is enqueued here and comes back with the RoI count (the
         # one host read the step needs anyway), so the host-side sampling further down overlaps the head's forward pass instead of waiting for it

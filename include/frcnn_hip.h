@@ -195,6 +195,18 @@ int frcnn_conv3x3_f32_cfg(const float *x, const float *w_packed, const float *bi
                           int Cout, int H, int W, int relu, int cfg, void *workspace,
                           size_t workspace_bytes, void *stream);
 int frcnn_maxpool2x2_f32(const float *x, float *y, int C, int H, int W, void *stream);
+/* Winograd F(2x2,3x3) form of the fp32 3x3 / pad 1 convolution (csrc/conv_wino.hip; the VGG-16 inference forward):
+ *   frcnn_wino_pack_w:      (Cout,Cin,3,3) (packed = 0) or frcnn_pack_conv3x3_w's [(ci*9+tap)][Cout] (packed = 1) -> U = G g G^T
+ *                           as [Cin][4][Cout][4] f32 (16 floats per (cout, cin), computed in double and rounded once; at load,
+ *                           and again after a trainer has updated the packed weights)
+ *   frcnn_conv3x3_wino_f32: act 0 = + b, 1 = + b, ReLU, 4 = + b, ReLU, 2x2/2 ceil-mode max-pool (y is Cout x ceil(H/2) x
+ *                           ceil(W/2)); fp32 operands and accumulation.  Cout % 64 == 0.  The workspace (caller-owned, no
+ *                           initialisation) holds the per-piece slabs of a launch split over K; its size:
+ *                           frcnn_conv_wino_workspace_bytes. */
+int frcnn_wino_pack_w(const float *w, int Cout, int Cin, int packed, float *u, void *stream);
+size_t frcnn_conv_wino_workspace_bytes(int Cin, int Cout, int H, int W);
+int frcnn_conv3x3_wino_f32(const float *x, const float *u, const float *bias, float *y, int Cin, int Cout, int H, int W, int act,
+                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- RPN 1x1 heads + the reference's 18-way softmax ------------------------------------------------
  * Replaces rpn_cls_score / F.softmax / rpn_bbox_pred (models/region_proposal_network.py:118-120).

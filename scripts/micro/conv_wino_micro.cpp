@@ -1,0 +1,90 @@
+// conv_wino_micro.cpp -- the Winograd F(2x2,3x3) fp32 convolution (frcnn_conv3x3_wino_f32) against the direct one (frcnn_conv_f32_ex) on the
+// VGG-16 layer shapes at 600 x 1000, without torch.  Per layer and arm: a captured graph of 5 back-to-back launches (outputs rotating over 3
+// buffers), bursts of graph launches between two events; the two arms alternate, `CONV_MICRO_REPS` rounds (default 3), median per arm.
+// Also the largest |wino - direct| / max|direct| per layer (a sanity check; tests/ hold the accuracy bars).
+// Usage: conv_wino_micro [layer ...]
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <algorithm>
+#include <random>
+#include <string>
+#include <vector>
+#include "frcnn_hip.h"
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
+
+struct Layer { const char *name; int ci, co, h, w, pool, times; };
+static const Layer kLayers[] = {
+    {"conv1_2", 64, 64, 600, 1000, 1, 1}, {"conv2_1", 64, 128, 300, 500, 0, 1}, {"conv2_2", 128, 128, 300, 500, 1, 1}, {"conv3_1", 128, 256, 150, 250, 0, 1},
+    {"conv3_2", 256, 256, 150, 250, 0, 1}, {"conv3_3", 256, 256, 150, 250, 1, 1}, {"conv4_1", 256, 512, 75, 125, 0, 1}, {"conv4_2", 512, 512, 75, 125, 0, 1},
+    {"conv4_3", 512, 512, 75, 125, 1, 1}, {"conv5_1", 512, 512, 38, 63, 0, 4}};
+
+int main(int argc, char **argv) {
+    std::vector<std::string> want;
+    for (int i = 1; i < argc; ++i) want.push_back(argv[i]);
+    hipStream_t s; CK(hipStreamCreate(&s));
+    const int burst = getenv("CONV_MICRO_BURST") ? atoi(getenv("CONV_MICRO_BURST")) : 8;
+    const int reps = getenv("CONV_MICRO_REPS") ? atoi(getenv("CONV_MICRO_REPS")) : 3;
+    std::mt19937 g(1); std::uniform_real_distribution<float> u(-1.f, 1.f);
+    double tot[2] = {0, 0};
+    for (const Layer &L : kLayers) {
+        if (!want.empty() && std::find(want.begin(), want.end(), std::string(L.name)) == want.end()) continue;
+        const int OH = L.pool ? (L.h + 1) / 2 : L.h, OW = L.pool ? (L.w + 1) / 2 : L.w;
+        const size_t nx = (size_t)L.ci * L.h * L.w, nw = (size_t)9 * L.co * L.ci, ny = (size_t)L.co * OH * OW;
+        std::vector<float> hx(nx), hw(nw), hb(L.co);
+        for (auto &e : hx) e = u(g);
+        for (auto &e : hw) e = 0.05f * u(g);
+        for (auto &e : hb) e = 0.1f * u(g);
+        float *dx, *dw, *dwp, *du, *db, *dy[2][3]; void *ws[2];
+        CK(hipMalloc(&dx, nx * 4)); CK(hipMalloc(&dw, nw * 4)); CK(hipMalloc(&dwp, nw * 4)); CK(hipMalloc(&du, nw / 9 * 16 * 4)); CK(hipMalloc(&db, L.co * 4));
+        for (auto &a : dy) for (auto &p : a) CK(hipMalloc(&p, ny * 4));
+        const size_t wsb[2] = {frcnn_conv3x3_workspace_bytes(L.ci, L.co, L.h, L.w), frcnn_conv_wino_workspace_bytes(L.ci, L.co, L.h, L.w)};
+        CK(hipMalloc(&ws[0], wsb[0])); CK(hipMalloc(&ws[1], wsb[1]));
+        if (frcnn_conv3x3_workspace_init(ws[0], wsb[0], s) != 0) { printf("workspace init failed\n"); return 1; }
+        CK(hipMemcpy(dx, hx.data(), nx * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dw, hw.data(), nw * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(db, hb.data(), L.co * 4, hipMemcpyHostToDevice));
+        if (frcnn_pack_conv3x3_w(dw, L.co, L.ci, dwp, s) != 0 || frcnn_wino_pack_w(dw, L.co, L.ci, 0, du, s) != 0) { printf("pack failed\n"); return 1; }
+        const double gflop = 2.0 * L.h * L.w * L.co * L.ci * 9 / 1e9;
+        hipGraphExec_t ge[2];
+        for (int arm = 0; arm < 2; ++arm) {
+            hipGraph_t gr;
+            CK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
+            bool ok = true;
+            for (int i = 0; i < 5; ++i)
+                ok = ok && (arm == 0 ? frcnn_conv_f32_ex(dx, dwp, db, nullptr, dy[0][i % 3], L.ci, L.co, L.h, L.w, 3, L.pool ? 4 : 1, ws[0], wsb[0], s)
+                                     : frcnn_conv3x3_wino_f32(dx, du, db, dy[1][i % 3], L.ci, L.co, L.h, L.w, L.pool ? 4 : 1, ws[1], wsb[1], s)) == 0;
+            CK(hipStreamEndCapture(s, &gr));
+            if (!ok) { printf("%s: launch refused (arm %d)\n", L.name, arm); return 1; }
+            CK(hipGraphInstantiate(&ge[arm], gr, nullptr, nullptr, 0));
+            CK(hipGraphDestroy(gr));
+            for (int i = 0; i < 2; ++i) CK(hipGraphLaunch(ge[arm], s));
+        }
+        CK(hipStreamSynchronize(s));
+        // sanity: the two arms' outputs
+        std::vector<float> y0(ny), y1(ny);
+        CK(hipMemcpy(y0.data(), dy[0][1], ny * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(y1.data(), dy[1][1], ny * 4, hipMemcpyDeviceToHost));
+        double md = 0, mx = 0;
+        for (size_t i = 0; i < ny; ++i) { md = std::max(md, (double)fabsf(y0[i] - y1[i])); mx = std::max(mx, (double)fabsf(y0[i])); }
+        hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        std::vector<float> us[2];
+        for (int r = 0; r < reps * 3; ++r)
+            for (int arm = 0; arm < 2; ++arm) {
+                CK(hipEventRecord(e0, s));
+                for (int b = 0; b < burst; ++b) CK(hipGraphLaunch(ge[arm], s));
+                CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
+                float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1)); us[arm].push_back(ms * 200.f / burst);
+            }
+        double med[2];
+        for (int arm = 0; arm < 2; ++arm) { std::sort(us[arm].begin(), us[arm].end()); med[arm] = us[arm][us[arm].size() / 2]; tot[arm] += med[arm] * L.times; }
+        printf("%-8s %3d->%3d %4dx%-4d %s direct %7.1f us  wino %7.1f us  (x%.2f; direct %6.1f TFLOP/s)  max|wino-direct|/max|direct| %.2e\n", L.name, L.ci, L.co,
+               L.h, L.w, L.pool ? "relu+pool" : "relu     ", med[0], med[1], med[0] / med[1], gflop / med[0] * 1e3, md / (mx > 0 ? mx : 1));
+        fflush(stdout);
+        for (auto &x : ge) CK(hipGraphExecDestroy(x));
+        CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(dwp)); CK(hipFree(du)); CK(hipFree(db)); CK(hipFree(ws[0])); CK(hipFree(ws[1]));
+        for (auto &a : dy) for (auto &p : a) CK(hipFree(p));
+    }
+    printf("chain (conv5_1 x 4; conv1_1 not included): direct %.1f us, wino %.1f us\n", tot[0], tot[1]);
+    return 0;
+}
