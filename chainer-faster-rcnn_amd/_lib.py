@@ -71,6 +71,11 @@ SIGNATURES = {
     "frcnn_conv_wgrad_f32s": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_conv1_f32s_train": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "frcnn_conv3x3_f32s_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_bf16_pack_many": (_I, [_P, _I, _P]),
+    "frcnn_conv1_bf16_train": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "frcnn_conv3x3_bf16_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_conv_wgrad_bf16_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "frcnn_conv_wgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_f32s_split": (_I, [_P, _S, _P, _P]),
     "frcnn_f32s_join": (_I, [_P, _S, _P, _P]),
     "frcnn_linear_f32s_workspace_bytes": (_S, [_I, _I, _I]),

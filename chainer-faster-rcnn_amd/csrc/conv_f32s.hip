@@ -34,7 +34,9 @@ constexpr int kParts = 3;
 __device__ __forceinline__ void split3_pair(float v0, float v1, uint32_t &h, uint32_t &m, uint32_t &l) { frcnn_split3_pair(v0, v1, h, m, l); }
 
 // ABL = timing ablations (WRONG results; scripts/conv_f32s_bench.py only): 1 no DMA, 4 no fragment reads / MFMAs
-template <int WPS, int ABL = 0, int NS = 1>
+// NP = operand parts: 3 = the split-product kernel above; 1 = the bf16 training form (only the h terms exist: operands and output are
+// the plain channel-blocked bf16 tensors of conv_bf16.hip, one h.h MFMA per fragment pair, a 26 KB stage per K-chunk)
+template <int WPS, int ABL = 0, int NS = 1, int NP = kParts>
 __global__ void __launch_bounds__(256, WPS)
 conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp, const float *__restrict__ bias, void *__restrict__ y,
                  int CinP, int Cout, int CoutP, int H, int W, int relu, int out_mode, int xtiles, int ytiles, int nsplit,
@@ -44,16 +46,17 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
     constexpr int RW = 2, BROWS = 4, BCO = 64;
     constexpr int HR = BROWS + KS - 1, HPX = 32 + KS - 1;
     constexpr int IN_ROWS = HR * HPX;                         // 204 halo pixels per part, 32 B each
-    constexpr int IN_ROWS_P = 208;                            // padded to a multiple of 16 rows: the swizzle phase is the same in every part
+    // padded to a multiple of 16 rows (the swizzle phase is the same in every part) and, with one part, to whole groups of four pieces
+    constexpr int IN_ROWS_P = NP == kParts ? 208 : 256;
     constexpr int W_ROWS = TAPS * BCO;                        // 576 weight rows per part
-    constexpr int IN_PIECES = (kParts * IN_ROWS_P * 2 + 63) / 64;   // 1 KB pieces (64 lanes x 16 B): 20
-    constexpr int W_PIECES = kParts * W_ROWS * 2 / 64;        // 54
+    constexpr int IN_PIECES = (NP * IN_ROWS_P * 2 + 63) / 64; // 1 KB pieces (64 lanes x 16 B): 20 (NP = 1: 8)
+    constexpr int W_PIECES = NP * W_ROWS * 2 / 64;            // 54 (NP = 1: 18)
     constexpr int PIECES = IN_PIECES + W_PIECES;              // 74
     constexpr int IN_BYTES = IN_PIECES * 1024, STAGE_BYTES = PIECES * 1024;
     constexpr int PPW = (PIECES + 3) / 4;                     // pieces per wave (wave w moves pieces w, w+4, ...)
     static_assert(IN_PIECES % 4 == 0, "a group of four pieces comes from one tensor");
     constexpr int OP = BCO * 2 + 16;                          // epilogue tile: LDS bytes per pixel and part (128 B + pad)
-    static_assert(kParts * BROWS * 32 * OP <= STAGE_BYTES, "epilogue tiles must fit in the stage");
+    static_assert(NP * BROWS * 32 * OP <= STAGE_BYTES, "epilogue tiles must fit in the stage");
     __shared__ __attribute__((aligned(1024))) unsigned char ring[NS * STAGE_BYTES];
     __shared__ int s_ticket;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -80,8 +83,8 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
     const int all_chunks = CinP / kCK;
     const int c_first = split * all_chunks / nsplit, nchunks = (split + 1) * all_chunks / nsplit - c_first;
     const uint32_t x_part_bytes = (uint32_t)((size_t)H * W * CinP * 2), w_part_bytes = (uint32_t)((size_t)TAPS * CoutP * CinP * 2);
-    const frcnn_buf_t xbuf = frcnn_make_buf(x, kParts * x_part_bytes);
-    const frcnn_buf_t wbuf = frcnn_make_buf(wp, kParts * w_part_bytes);
+    const frcnn_buf_t xbuf = frcnn_make_buf(x, NP * x_part_bytes);
+    const frcnn_buf_t wbuf = frcnn_make_buf(wp, NP * w_part_bytes);
     const uint32_t x_chunk_bytes = (uint32_t)(H * W) * 32u, w_chunk_bytes = (uint32_t)(TAPS * CoutP) * 32u;
 
     // source offset (chunk 0) of the 16 bytes this lane contributes to each of its wave's pieces: slot s of a region holds
@@ -95,7 +98,7 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
             const int part = R / IN_ROWS_P, P = R - part * IN_ROWS_P;
             const int hr = P / HPX, hx = P - hr * HPX;
             const int gy = y0 - PAD + hr, gx = x0 - PAD + hx;
-            const bool inside = part < kParts && P < IN_ROWS && gy >= 0 && gy < H && gx >= 0 && gx < W;
+            const bool inside = part < NP && P < IN_ROWS && gy >= 0 && gy < H && gx >= 0 && gx < W;
             poff[q] = inside ? (uint32_t)part * x_part_bytes + (uint32_t)((gy * W + gx) * 32 + half * 16) : kBufOob;
         } else {
             const int sl = (pid - IN_PIECES) * 64 + lane, R = sl >> 1, half = (sl & 1) ^ ((R >> 3) & 1);
@@ -140,9 +143,9 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
         const unsigned char *st = ring + stage * STAGE_BYTES;
 #pragma unroll
         for (int ky = 0; ky < KS; ++ky) {
-            uint4 a[kParts][KS], b[kParts][RW][KS];
+            uint4 a[NP][KS], b[NP][RW][KS];
 #pragma unroll
-            for (int p = 0; p < kParts; ++p)
+            for (int p = 0; p < NP; ++p)
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx) {
                     if constexpr ((ABL & 8) != 0) {                   // no fragment reads: the MFMA ceiling of this loop
@@ -155,6 +158,16 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
                     for (int j = 0; j < RW; ++j) b[p][j][kx] = *reinterpret_cast<const uint4 *>(st + b_off[ky + j][kx] + p * IN_ROWS_P * 32);
                     }
                 }
+            if constexpr (NP == 1) {
+                // h.h only; the middle tap column goes to the second accumulator set: four independent chains per wave, as above
+#pragma unroll
+                for (int kx = 0; kx < KS; ++kx)
+#pragma unroll
+                    for (int j = 0; j < RW; ++j) {
+                        if (kx == 1) acs[j] = frcnn_mfma_32x32x16_bf16(a[0][kx], b[0][j][kx], acs[j]);
+                        else acc[j] = frcnn_mfma_32x32x16_bf16(a[0][kx], b[0][j][kx], acc[j]);
+                    }
+            } else {
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
 #pragma unroll
@@ -169,6 +182,7 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
                 for (int j = 0; j < RW; ++j) acs[j] = frcnn_mfma_32x32x16_bf16(a[1][kx], b[1][j][kx], acs[j]);     // m.m
 #pragma unroll
                 for (int j = 0; j < RW; ++j) acc[j] = frcnn_mfma_32x32x16_bf16(a[0][kx], b[0][j][kx], acc[j]);     // h.h
+            }
             }
         }
     };
@@ -331,12 +345,14 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
                 const int colc = wco * 32 + 8 * g + 4 * khalf;                 // first of four consecutive couts (within the tile)
                 unsigned char *o = ring + (wrow * 16 + (l31 >> 1)) * OP + colc * 2;
                 *reinterpret_cast<uint2 *>(o) = make_uint2(hp[0], hp[1]);
-                *reinterpret_cast<uint2 *>(o + (BROWS / 2) * 16 * OP) = make_uint2(mp[0], mp[1]);
-                *reinterpret_cast<uint2 *>(o + 2 * (BROWS / 2) * 16 * OP) = make_uint2(lp[0], lp[1]);
+                if constexpr (NP == kParts) {
+                    *reinterpret_cast<uint2 *>(o + (BROWS / 2) * 16 * OP) = make_uint2(mp[0], mp[1]);
+                    *reinterpret_cast<uint2 *>(o + 2 * (BROWS / 2) * 16 * OP) = make_uint2(lp[0], lp[1]);
+                }
             }
         }
         __syncthreads();
-        for (int e = tid; e < kParts * (BROWS / 2) * 16 * 8; e += 256) {       // 16-byte vectors: (part, cout block of 16, pooled pixel, half)
+        for (int e = tid; e < NP * (BROWS / 2) * 16 * 8; e += 256) {       // 16-byte vectors: (part, cout block of 16, pooled pixel, half)
             const int part = e / ((BROWS / 2) * 16 * 8), e1 = e - part * ((BROWS / 2) * 16 * 8);
             const int cbl = e1 / ((BROWS / 2) * 16 * 2), rem = e1 - cbl * ((BROWS / 2) * 16 * 2);
             const int opix = rem >> 1, half = rem & 1;
@@ -359,12 +375,14 @@ conv_f32s_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ wp
             split3_pair(v[j][4 * g + 2], v[j][4 * g + 3], hp[1], mp[1], lp[1]);
             const int colc = wco * 32 + 8 * g + 4 * khalf;
             unsigned char *o = ring + ((wrow * RW + j) * 32 + l31) * OP + colc * 2;
-            *reinterpret_cast<uint2 *>(o) = make_uint2(hp[0], hp[1]);
-            *reinterpret_cast<uint2 *>(o + BROWS * 32 * OP) = make_uint2(mp[0], mp[1]);
-            *reinterpret_cast<uint2 *>(o + 2 * BROWS * 32 * OP) = make_uint2(lp[0], lp[1]);
+            *reinterpret_cast<uint2 *>(o) = make_uint2(hp[0], hp[1]);                 // (NP = 1: h = RNE of the fp32 value)
+            if constexpr (NP == kParts) {
+                *reinterpret_cast<uint2 *>(o + BROWS * 32 * OP) = make_uint2(mp[0], mp[1]);
+                *reinterpret_cast<uint2 *>(o + 2 * BROWS * 32 * OP) = make_uint2(lp[0], lp[1]);
+            }
         }
     __syncthreads();
-    for (int e = tid; e < kParts * BROWS * 32 * 8; e += 256) {                 // 16-byte vectors: (part, cout block of 16, pixel, half)
+    for (int e = tid; e < NP * BROWS * 32 * 8; e += 256) {                 // 16-byte vectors: (part, cout block of 16, pixel, half)
         const int part = e / (BROWS * 32 * 8), e1 = e - part * (BROWS * 32 * 8);
         const int cbl = e1 / (BROWS * 32 * 2), rem = e1 - cbl * (BROWS * 32 * 2);
         const int pix = rem >> 1, half = rem & 1;
@@ -670,7 +688,8 @@ pack_w_f32s_from_packed_kernel(const float *__restrict__ wp, int Cin, int Cout, 
     dst[i] = (uint16_t)h; dst[total + i] = (uint16_t)m; dst[2 * total + i] = (uint16_t)l;
 }
 
-// All layers of a trainer in ONE launch (26 launches of 8 us each otherwise, every step): up to 16 layers, each block looks its layer up
+// All layers of a trainer in ONE launch (26 launches of 8 us each otherwise, every step): up to 16 layers, each block looks its layer up.
+// NP = 1: the bf16 training step's weights -- only the h term, RNE of the fp32 weight, i.e. frcnn_bf16_pack_conv_w of it
 struct PackManyArgs {
     const float *wp[16];
     uint16_t *fwd[16], *dgr[16];
@@ -678,6 +697,7 @@ struct PackManyArgs {
     unsigned block_end[16];                          // exclusive prefix of 256-element blocks
     int n;
 };
+template <int NP = kParts>
 __global__ void __launch_bounds__(256)
 pack_w_f32s_many_kernel(const PackManyArgs a) {
     int li = 0;
@@ -695,7 +715,8 @@ pack_w_f32s_many_kernel(const PackManyArgs a) {
         uint32_t h, m, l;
         split3_pair((o < Cout && k < Cin) ? wp[((size_t)k * 9 + tap) * Cout + o] : 0.0f, 0.0f, h, m, l);
         uint16_t *d = a.fwd[li];
-        d[i] = (uint16_t)h; d[total + i] = (uint16_t)m; d[2 * total + i] = (uint16_t)l;
+        d[i] = (uint16_t)h;
+        if constexpr (NP == kParts) { d[total + i] = (uint16_t)m; d[2 * total + i] = (uint16_t)l; }
     }
     if (a.dgr[li] != nullptr) {   // input gradient: [CoutP/16][tap][CinP][16], taps rotated
         const int c16 = (int)(i % 16), o = (int)((i / 16) % CinP), tap = (int)((i / (16 * (size_t)CinP)) % 9);
@@ -703,7 +724,8 @@ pack_w_f32s_many_kernel(const PackManyArgs a) {
         uint32_t h, m, l;
         split3_pair((o < Cin && k < Cout) ? wp[((size_t)o * 9 + (8 - tap)) * Cout + k] : 0.0f, 0.0f, h, m, l);
         uint16_t *d = a.dgr[li];
-        d[i] = (uint16_t)h; d[total + i] = (uint16_t)m; d[2 * total + i] = (uint16_t)l;
+        d[i] = (uint16_t)h;
+        if constexpr (NP == kParts) { d[total + i] = (uint16_t)m; d[2 * total + i] = (uint16_t)l; }
     }
 }
 
@@ -764,7 +786,7 @@ int frcnn_f32s_pack_from_packed(const float *w_packed_f32, int Cin, int Cout, in
     return frcnn_launch_status();
 }
 
-int frcnn_f32s_pack_many(const frcnn_f32s_pack_desc *layers, int n, void *stream) {
+static int pack_many_launch(const frcnn_f32s_pack_desc *layers, int n, bool split, hipStream_t stream) {
     if (!layers || n < 1 || n > 16) return FRCNN_ERR_INVALID;
     PackManyArgs a;
     memset(&a, 0, sizeof(a));
@@ -778,9 +800,14 @@ int frcnn_f32s_pack_many(const frcnn_f32s_pack_desc *layers, int n, void *stream
         a.block_end[i] = blocks;
     }
     a.n = n;
-    hipLaunchKernelGGL(pack_w_f32s_many_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (split) hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_f32s_many_kernel<kParts>), dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_f32s_many_kernel<1>), dim3(blocks), dim3(256), 0, stream, a);
     return frcnn_launch_status();
 }
+
+int frcnn_f32s_pack_many(const frcnn_f32s_pack_desc *layers, int n, void *stream) { return pack_many_launch(layers, n, true, (hipStream_t)stream); }
+
+int frcnn_bf16_pack_many(const frcnn_bf16_pack_desc *layers, int n, void *stream) { return pack_many_launch(layers, n, false, (hipStream_t)stream); }
 
 int frcnn_f32s_from_nchw_f32(const float *x, int C, int H, int W, uint16_t *y, void *stream) {
     if (!x || !y || C < 1 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
@@ -826,6 +853,22 @@ int frcnn_conv1_f32s_train(const float *x, const float *w_packed_f32, const floa
     const dim3 grid(conv1_grid(ntiles, true));
 #define FRCNN_CONV1_TRAIN(NCB, DUAL_) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1_f32s_kernel<NCB, true, DUAL_>), grid, dim3(256), 0, (hipStream_t)stream, x, \
                                                          w_packed_f32, bias, y_split, Cin, Cout, H, W, relu, 1, y_nchw, xtiles, ntiles)
+    if (y_nchw != nullptr) { if (Cout > 32) FRCNN_CONV1_TRAIN(2, true); else FRCNN_CONV1_TRAIN(1, true); }
+    else { if (Cout > 32) FRCNN_CONV1_TRAIN(2, false); else FRCNN_CONV1_TRAIN(1, false); }
+#undef FRCNN_CONV1_TRAIN
+    return frcnn_launch_status();
+}
+
+// conv1_1 of the bf16 training step: the first-layer kernel's plain bf16 form (operands RNE-rounded in registers, one MFMA per k-step)
+// on the trainers' packed fp32 weights, y_bf16 = RNE(y_nchw) -- both from the same fp32 epilogue value
+int frcnn_conv1_bf16_train(const float *x, const float *w_packed_f32, const float *bias, uint16_t *y_bf16, float *y_nchw, int Cin, int Cout, int H, int W,
+                           int relu, void *stream) {
+    if (!x || !w_packed_f32 || !bias || !y_bf16 || Cin < 1 || Cin > 3 || Cout < 1 || Cout > 64 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
+    if ((size_t)H * W * 64 * 4 >= (1ull << 31)) return FRCNN_ERR_INVALID;          // the fp32 map behind a 32-bit buffer range
+    const int xtiles = frcnn_cdiv(W, 64), ntiles = xtiles * frcnn_cdiv(H, 4);
+    const dim3 grid(conv1_grid(ntiles, false, y_nchw != nullptr && Cout > 32 ? 2 : 4));  // the dual 64-cout form's 65 KB of LDS seats two per CU
+#define FRCNN_CONV1_TRAIN(NCB, DUAL_) hipLaunchKernelGGL(HIP_KERNEL_NAME(conv1_f32s_kernel<NCB, false, DUAL_>), grid, dim3(256), 0, (hipStream_t)stream, x, \
+                                                         w_packed_f32, bias, y_bf16, Cin, Cout, H, W, relu, 1, y_nchw, xtiles, ntiles)
     if (y_nchw != nullptr) { if (Cout > 32) FRCNN_CONV1_TRAIN(2, true); else FRCNN_CONV1_TRAIN(1, true); }
     else { if (Cout > 32) FRCNN_CONV1_TRAIN(2, false); else FRCNN_CONV1_TRAIN(1, false); }
 #undef FRCNN_CONV1_TRAIN
@@ -945,6 +988,45 @@ int frcnn_conv3x3_f32s_train(const uint16_t *x, const uint16_t *w_packed, const 
     if (!y_split && !y_nchw) return FRCNN_ERR_INVALID;
     if (!y_split) return conv3x3_f32s_launch(x, w_packed, bias, y_nchw, nullptr, mask, Cin, Cout, H, W, relu, 1, workspace, workspace_bytes, (hipStream_t)stream);
     return conv3x3_f32s_launch(x, w_packed, bias, y_split, y_nchw, mask, Cin, Cout, H, W, relu, 0, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// The bf16 training form: conv_f32s_kernel with ONE operand part (NP = 1).  The stage is 26 KB instead of 74 KB and the registers of
+// two fragment sets are gone, so FOUR workgroups share a CU (kBf16tWps) -- the co-resident workgroups' MFMAs cover each other's staging.
+// Split-K (same workspace and counter-page contract as the split kernel) for launches that cannot fill those slots once.
+constexpr int kBf16tWps = 4;
+static int conv_bf16t_pick_split(long tiles, int chunks) {
+    const char *e = frcnn_tune("FRCNN_BF16T_SPLIT");
+    const long slots = (long)kBf16tWps * frcnn_cu_count();
+    int s = e ? atoi(e) : (tiles > kF32sMaxSplitTiles ? 1 : (int)(slots / (tiles > 0 ? tiles : 1)));
+    if (s > 4) s = 4;
+    if (s < 1) s = 1;
+    while (s > 1 && chunks / s < 4) --s;                          // a split should still carry a few chunks
+    return s;
+}
+
+int frcnn_conv3x3_bf16_train(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y_bf16, float *y_nchw, const float *mask, int Cin,
+                             int Cout, int H, int W, int relu, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!x || !w_packed || !bias || (!y_bf16 && !y_nchw) || Cin < 1 || Cout < 1 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
+    const int CinP = (Cin + 15) / 16 * 16, CoutP = (Cout + 15) / 16 * 16;
+    if ((size_t)H * W * CinP * 2 >= (1ull << 31) || (size_t)9 * CoutP * CinP * 2 >= (1ull << 31) || (size_t)H * W * CoutP * 2 >= (1ull << 31)) return FRCNN_ERR_INVALID;
+    if ((size_t)Cout * H * W * 4 >= (1ull << 31)) return FRCNN_ERR_INVALID;             // the fp32 maps sit behind 32-bit buffer ranges
+    const int xtiles = frcnn_cdiv(W, 32), ytiles = frcnn_cdiv(H, 4), cotiles = frcnn_cdiv(CoutP, 64);
+    const long tiles = (long)xtiles * ytiles * cotiles;
+    int nsplit = 1;
+    if (workspace && tiles * 4 <= 16384) {
+        nsplit = conv_bf16t_pick_split(tiles, CinP / kCK);
+        if (workspace_bytes < kF32sCounterPageBytes + (size_t)tiles * nsplit * 256 * 32 * sizeof(float)) nsplit = 1;
+    }
+    float *partials = nsplit > 1 ? (float *)((char *)workspace + kF32sCounterPageBytes) : nullptr;
+    int *counters = nsplit > 1 ? (int *)workspace : nullptr;
+    // y_bf16 == NULL: the fp32 NCHW map only (out_mode 1 through the training epilogue's mask); else the blocked bf16 tensor (out_mode 0)
+    // and, when y_nchw is given, the fp32 map from the same fp32 value
+    void *y = y_bf16 ? (void *)y_bf16 : (void *)y_nchw;
+    float *yn = y_bf16 ? y_nchw : nullptr;
+    const int out_mode = y_bf16 ? 0 : 1;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_f32s_kernel<kBf16tWps, 0, 1, 1>), dim3((unsigned)(tiles * nsplit)), dim3(256), 0, (hipStream_t)stream, x, w_packed,
+                       bias, y, CinP, Cout, CoutP, H, W, relu, out_mode, xtiles, ytiles, nsplit, partials, counters, 0, yn, mask);
+    return frcnn_launch_status();
 }
 
 int frcnn_conv3x3_f32s(const uint16_t *x, const uint16_t *w_packed, const float *bias, void *y, int Cin, int Cout, int H, int W, int relu, int out_mode,

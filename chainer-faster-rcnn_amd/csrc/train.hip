@@ -775,7 +775,11 @@ conv1_wgrad_kernel(const float *__restrict__ x, const float *__restrict__ dy, fl
 // operands a step needs are 17 KB per 108 MFMAs (the forward kernel: 74 KB) -- this kernel is bound by the matrix pipe, not by
 // staging.  One workgroup per CU (104 KB of LDS, 144 accumulator registers); the next tile's global loads are in flight during the
 // current tile's MFMAs.  Slabs, split order and the reduce pass are the fp32 kernel's.
+// NP = 1: the bf16 training step's form -- x and dy rounded to bf16 (RNE) while they are staged, one h.h MFMA per fragment pair (9 per
+// 16-pixel step and tap row instead of 54), 45 KB of LDS.  Still one workgroup per CU: the 144 accumulators, the next tile's 72 staging
+// registers and the per-thread staging offsets need ~330 VGPRs (at two workgroups per CU, 256, it spills).
 constexpr int kSRows = 3;                      // tile rows of the split kernel (x halo: 5 rows; 135 KB of LDS)
+template <int NP = 3>
 __global__ void __launch_bounds__(256, 1)
 conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ slabs, int Cin, int Cout, int H, int W,
                        int xtiles, int nblocks, int splits) {
@@ -784,8 +788,8 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
     constexpr int DROW = 64, DCH = kSRows * DROW + 16;         // a dy row (32 px), a channel
     static_assert((XCH / 16) % 2 == 1 && (DCH / 16) % 2 == 1, "channel pitches must be odd multiples of 16 bytes");
     constexpr int XPART = 64 * XCH, DPART = 64 * DCH;
-    __shared__ __attribute__((aligned(16))) unsigned char x_lds[3 * XPART];
-    __shared__ __attribute__((aligned(16))) unsigned char dy_lds[3 * DPART];
+    __shared__ __attribute__((aligned(16))) unsigned char x_lds[NP * XPART];
+    __shared__ __attribute__((aligned(16))) unsigned char dy_lds[NP * DPART];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wci = wave & 1, wco = wave >> 1;
@@ -857,8 +861,10 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
             frcnn_split3_pair(xv[q][2], xv[q][3], h1, m1, l1);
             unsigned char *d = x_lds + x_lo[q];                       // (4-byte aligned: two dword stores per part)
             *reinterpret_cast<uint32_t *>(d) = h0; *reinterpret_cast<uint32_t *>(d + 4) = h1;
-            *reinterpret_cast<uint32_t *>(d + XPART) = m0; *reinterpret_cast<uint32_t *>(d + XPART + 4) = m1;
-            *reinterpret_cast<uint32_t *>(d + 2 * XPART) = l0; *reinterpret_cast<uint32_t *>(d + 2 * XPART + 4) = l1;
+            if constexpr (NP == 3) {
+                *reinterpret_cast<uint32_t *>(d + XPART) = m0; *reinterpret_cast<uint32_t *>(d + XPART + 4) = m1;
+                *reinterpret_cast<uint32_t *>(d + 2 * XPART) = l0; *reinterpret_cast<uint32_t *>(d + 2 * XPART + 4) = l1;
+            }
         }
 #pragma unroll
         for (int q = 0; q < DQ; ++q) {
@@ -868,8 +874,10 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
             frcnn_split3_pair(dv[q][2], dv[q][3], h1, m1, l1);
             unsigned char *d = dy_lds + d_lo[q];                      // 8-byte aligned
             *reinterpret_cast<uint2 *>(d) = make_uint2(h0, h1);
-            *reinterpret_cast<uint2 *>(d + DPART) = make_uint2(m0, m1);
-            *reinterpret_cast<uint2 *>(d + 2 * DPART) = make_uint2(l0, l1);
+            if constexpr (NP == 3) {
+                *reinterpret_cast<uint2 *>(d + DPART) = make_uint2(m0, m1);
+                *reinterpret_cast<uint2 *>(d + 2 * DPART) = make_uint2(l0, l1);
+            }
         }
     };
     auto compute = [&]() {
@@ -879,11 +887,11 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
         // the raw reads of unit u+1 are issued BEFORE the MFMAs of unit u (register double buffer, two units per trip so that it is
         // indexed statically); the compiler's own schedule read each fragment right before its use: 9 exposed round trips per step
         constexpr int NU = kSRows * 2 * 3;
-        struct Raw { uint4 mid[3]; uint32_t lo[3], hi[3]; uint4 b[3]; };
+        struct Raw { uint4 mid[NP]; uint32_t lo[NP], hi[NP]; uint4 b[NP]; };
         auto load = [&](int u, Raw &w) {
             const int sidx = u / 3, ky = u - sidx * 3, r = sidx >> 1, ks = sidx & 1;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
+            for (int p = 0; p < NP; ++p) {
                 const unsigned char *row = xa + p * XPART + (r + ky) * XROW + ks * 32;
                 w.mid[p] = *reinterpret_cast<const uint4 *>(row);
                 w.lo[p] = *reinterpret_cast<const uint32_t *>(row - 4);
@@ -892,15 +900,19 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
             }
         };
         auto mfmas = [&](int ky, const Raw &w) {
-            uint4 a[3][3];                                                               // [part][kx]
+            uint4 a[NP][3];                                                              // [part][kx]
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
+            for (int p = 0; p < NP; ++p) {
                 const uint4 mid = w.mid[p];
                 const uint32_t s01 = frcnn_alignbit(mid.y, mid.x, 16), s12 = frcnn_alignbit(mid.z, mid.y, 16), s23 = frcnn_alignbit(mid.w, mid.z, 16);
                 a[p][0] = make_uint4(frcnn_alignbit(mid.x, w.lo[p], 16), s01, s12, s23);   // pixels -1 .. +6: tap column 0
                 a[p][1] = mid;
                 a[p][2] = make_uint4(s01, s12, s23, frcnn_alignbit(w.hi[p], mid.w, 16));   // pixels +1 .. +8: tap column 2
             }
+            if constexpr (NP == 1) {
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = frcnn_mfma_32x32x16_bf16(a[0][kx], w.b[0], acc[ky * 3 + kx]);     // h.h
+            } else {
             // six products per tap; the three taps of the row take turns so that consecutive MFMAs never share an accumulator
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = frcnn_mfma_32x32x16_bf16(a[2][kx], w.b[0], acc[ky * 3 + kx]);     // l.h
@@ -914,6 +926,7 @@ conv_wgrad_f32s_kernel(const float *__restrict__ x, const float *__restrict__ dy
             for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = frcnn_mfma_32x32x16_bf16(a[0][kx], w.b[1], acc[ky * 3 + kx]);     // h.m
 #pragma unroll
             for (int kx = 0; kx < 3; ++kx) acc[ky * 3 + kx] = frcnn_mfma_32x32x16_bf16(a[0][kx], w.b[0], acc[ky * 3 + kx]);     // h.h
+            }
         };
         static_assert(NU % 6 == 0, "six units per trip: the tap row index is static");
         Raw w0, w1;
@@ -1415,11 +1428,49 @@ int frcnn_conv_wgrad_f32s(const float *x, const float *dy, float *dw_packed, int
     if (s > p.nblocks) s = p.nblocks;
     if (s < 1) s = 1;
     float *slabs = (float *)workspace;
-    hipLaunchKernelGGL(conv_wgrad_f32s_kernel, dim3(p.ci_tiles, p.co_tiles, s), dim3(256), 0, stream, x, dy, slabs, Cin, Cout, H, W, p.xtiles, p.nblocks, s);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_f32s_kernel<3>), dim3(p.ci_tiles, p.co_tiles, s), dim3(256), 0, stream, x, dy, slabs, Cin, Cout, H, W, p.xtiles, p.nblocks, s);
     const size_t n = p.slab_floats;
     const size_t work = (n / 4 + 255) / 256 + 1;
     const int blocks = (int)(work < 4096 ? work : 4096);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, slabs, n, s, dw_packed);
+    return frcnn_launch_status();
+}
+
+// bf16 form (conv_wgrad_f32s_kernel<1>): one workgroup per CU as the split kernel, but its own plan and workspace size (the split
+// kernel borrows the fp32 kernel's); FRCNN_WGRAD_BF16_SPLITS overrides the pixel splits (at most two per CU)
+static WgradPlan plan_wgrad_bf16(int Cin, int Cout, int H, int W) {
+    WgradPlan p = plan_wgrad(Cin, Cout, H, W, 3);
+    p.nblocks = p.xtiles * frcnn_cdiv(H, kSRows);
+    int s = frcnn_cdiv(frcnn_cu_count(), p.ci_tiles * p.co_tiles);
+    const int se = frcnn_tune_int("FRCNN_WGRAD_BF16_SPLITS", 0);
+    if (se > 0) s = se;
+    if (s > 2 * frcnn_cu_count()) s = 2 * frcnn_cu_count();
+    if (s > p.nblocks) s = p.nblocks;
+    if (s < 1) s = 1;
+    p.splits = s;
+    return p;
+}
+
+size_t frcnn_conv_wgrad_bf16_workspace_bytes(int Cin, int Cout, int H, int W) {
+    if (Cin < 1 || Cout < 1 || H < 1 || W < 1) return 0;
+    const WgradPlan p = plan_wgrad_bf16(Cin, Cout, H, W);
+    return frcnn_align256(p.slab_floats * p.splits * sizeof(float));
+}
+
+int frcnn_conv_wgrad_bf16(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace, size_t workspace_bytes,
+                          void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!x || !dy || !dw_packed || Cin < 1 || Cout < 1 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
+    if ((size_t)Cin * H * W * 4 >= (1ull << 31) || (size_t)Cout * H * W * 4 >= (1ull << 31)) return FRCNN_ERR_INVALID;
+    const WgradPlan p = plan_wgrad_bf16(Cin, Cout, H, W);
+    if (!workspace || workspace_bytes < p.slab_floats * p.splits * sizeof(float)) return FRCNN_ERR_INVALID;
+    float *slabs = (float *)workspace;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wgrad_f32s_kernel<1>), dim3(p.ci_tiles, p.co_tiles, p.splits), dim3(256), 0, stream, x, dy, slabs, Cin, Cout, H, W,
+                       p.xtiles, p.nblocks, p.splits);
+    const size_t n = p.slab_floats;
+    const size_t work = (n / 4 + 255) / 256 + 1;
+    const int blocks = (int)(work < 4096 ? work : 4096);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, slabs, n, p.splits, dw_packed);
     return frcnn_launch_status();
 }
 

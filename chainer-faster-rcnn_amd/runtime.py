@@ -643,6 +643,55 @@ class Runtime(object):
                                             m.stream()), "frcnn_conv1_f32s_train")
         return ys, yn
 
+    # ------------------------------------------------------------------ bf16 training forms (RPNTrainer(conv_math="bf16"); csrc/conv_f32s.hip, train.hip)
+    def bf16_pack_many(self, layers):
+        """layers: [(packed fp32 weights (cin*9, cout), bf16 fwd weights [CinP/16][9][CoutP][16], bf16 dgrad weights [CoutP/16][9][CinP][16] or None,
+        cin, cout)], at most 16: ONE launch; every weight is RNE(fp32)."""
+        import ctypes
+
+        class Desc(ctypes.Structure):
+            _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgr", ctypes.c_void_p), ("cin", ctypes.c_int), ("cout", ctypes.c_int)]
+        m, L = self.mem, self.lib
+        val = lambda t: None if t is None else m.ptr(t).value
+        arr = (Desc * len(layers))(*[Desc(val(w), val(f), val(d), int(ci), int(co)) for (w, f, d, ci, co) in layers])
+        _lib.check(L.frcnn_bf16_pack_many(ctypes.cast(arr, ctypes.c_void_p), len(layers), m.stream()), "frcnn_bf16_pack_many")
+
+    def conv3x3_bf16_train(self, x, w_packed, bias, cin, cout, relu=True, want_bf16=True, want_nchw=True, mask=None):
+        """x [CinP/16][H][W][16] bf16 -> (bf16 [CoutP/16][H][W][16] or None, (1,Cout,H,W) fp32 or None); mask (1,Cout,H,W) fp32.
+        bf16 products, fp32 accumulation and epilogue; the bf16 output is RNE of the fp32 one."""
+        m, L = self.mem, self.lib
+        H, W = int(x.shape[1]), int(x.shape[2])
+        assert int(x.shape[0]) * 16 == self.bf16_pad(cin) and int(w_packed.shape[0]) * 16 == self.bf16_pad(cin) and (want_bf16 or want_nchw)
+        yb = m.empty((self.bf16_pad(cout) // 16, H, W, 16), "i16") if want_bf16 else None
+        yn = m.empty((1, int(cout), H, W), "f32") if want_nchw else None
+        ws = self.workspace("conv_f32s", L.frcnn_conv_f32s_workspace_bytes(int(cin), int(cout), H, W),
+                            init=lambda w: _lib.check(L.frcnn_conv_f32s_workspace_init(m.ptr(w), w.shape[0], m.stream()),
+                                                      "frcnn_conv_f32s_workspace_init"))
+        _lib.check(L.frcnn_conv3x3_bf16_train(m.ptr(x), m.ptr(w_packed), m.ptr(bias), m.ptr(yb), m.ptr(yn), m.ptr(mask), int(cin), int(cout), H, W,
+                                              int(bool(relu)), m.ptr(ws), ws.shape[0], m.stream()), "frcnn_conv3x3_bf16_train")
+        return yb, yn
+
+    def conv1_bf16_train(self, x, w_packed_f32, bias, cout, relu=True):
+        """First layer, bf16 training form: x (1,Cin<=3,H,W) fp32, packed fp32 weights (cin*9, cout) -> (bf16 blocked, fp32 NCHW)."""
+        m, L = self.mem, self.lib
+        cin, H, W = [int(v) for v in x.shape[-3:]]
+        yb = m.empty((self.bf16_pad(cout) // 16, H, W, 16), "i16")
+        yn = m.empty((1, int(cout), H, W), "f32")
+        _lib.check(L.frcnn_conv1_bf16_train(m.ptr(x), m.ptr(w_packed_f32), m.ptr(bias), m.ptr(yb), m.ptr(yn), cin, int(cout), H, W, int(bool(relu)),
+                                            m.stream()), "frcnn_conv1_bf16_train")
+        return yb, yn
+
+    def conv_wgrad_bf16(self, x, dy, out=None):
+        """The 3x3 weight gradient on bf16 products of RNE(x), RNE(dy) with fp32 accumulation; same layout as conv_wgrad."""
+        m, L = self.mem, self.lib
+        ci, H, W = [int(v) for v in x.shape[-3:]]
+        co = int(dy.shape[-3])
+        dw = out if out is not None else m.empty((ci * 9, co), "f32")
+        ws = self.workspace("wgrad_bf16", L.frcnn_conv_wgrad_bf16_workspace_bytes(ci, co, H, W))
+        _lib.check(L.frcnn_conv_wgrad_bf16(m.ptr(x), m.ptr(dy), m.ptr(dw), ci, co, H, W, m.ptr(ws), ws.shape[0], m.stream()),
+                   "frcnn_conv_wgrad_bf16")
+        return dw
+
     def conv1_bf16(self, x, w, bias, relu=True):
         """First layer of the bf16 chain: x (1,Cin<=3,H,W) fp32 NCHW, w (Cout<=64,Cin,3,3) fp32 -> [CoutP/16][H][W][16] bf16."""
         if self.half == "f16":                 # no fp16 twin of the first-layer kernel (csrc/conv_f32s.hip): the generic convolution on the blocked image, Cin padded to 16

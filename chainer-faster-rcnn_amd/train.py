@@ -191,6 +191,69 @@ def trunk_backward_split(trainer, layer_inputs, g):
     return g
 
 
+def trunk_forward_bf16(trainer, x):
+    """trunk_forward with every convolution on bf16 operands and fp32 accumulation (RPNTrainer(conv_math="bf16")): conv1_1 on the
+    first-layer kernel (fp32 image and weights rounded in registers), the others on csrc/conv_f32s.hip's one-part form.  Every
+    convolution leaves its result as fp32 NCHW (what the weight gradient, pooling and the ReLU masks read) and, when a convolution
+    follows, as the blocked bf16 tensor RNE(fp32) that one reads.  Pools run on fp32.  -> (feat, inputs, feat_bf16)."""
+    model, rt = trainer.model, trainer.rt
+    rtb = rt.with_half("bf16")
+    layers = model.trunk.layers
+    inputs, h, hb = [], x, None
+    for idx, l in enumerate(layers):
+        inputs.append(h)
+        if l == "pool":
+            h, hb = rt.maxpool2x2(h), None
+            continue
+        name, link = l[0], model.trunk.links[l[0]]
+        if int(link.cin) <= 3 and int(link.cout) <= 64:              # conv1_1: the first-layer kernel, fp32 NCHW image in
+            hb, h = rt.conv1_bf16_train(h, link.Wp, link.b, link.cout, relu=True)
+            continue
+        if hb is None:
+            hb = rtb.bf16_from_nchw(h)
+        conv_next = idx + 1 == len(layers) or layers[idx + 1] != "pool"        # the last map feeds rpn_conv_3x3
+        hb, h = rt.conv3x3_bf16_train(hb, trainer.wb_fwd[name], link.b, link.cin, link.cout, relu=True, want_bf16=conv_next)
+    if hb is None:
+        hb = rtb.bf16_from_nchw(h)                                    # (trunks that end in a pool)
+    return h, inputs, hb
+
+
+def trunk_backward_bf16(trainer, layer_inputs, g):
+    """trunk_backward_split on bf16 operands: input-gradient convolutions on RNE(upstream gradient) and RNE(rotated weights) with the
+    ReLU mask fused, weight gradients on RNE(x), RNE(dy) (csrc/train.hip conv_wgrad_f32s_kernel<1>), bias gradients and pools in fp32."""
+    rt = trainer.rt
+    rtb = rt.with_half("bf16")
+    first = trainer.convs[0][0]
+    names = [l if l == "pool" else l[0] for l, _ in layer_inputs]
+    gb = None
+    for pos in range(len(layer_inputs) - 1, -1, -1):
+        l, xin = layer_inputs[pos]
+        if l == "pool":
+            if getattr(trainer, "keep_dy", None) is not None:
+                trainer.kept_dy.setdefault("pool_inputs", []).append(xin)
+            g, gb = rt.maxpool2x2_bwd(xin, g), None
+            continue
+        name = l[0]
+        keep = getattr(trainer, "keep_dy", None)
+        if keep is not None and name in keep:
+            trainer.kept_dy[name] = (xin, g.clone() if hasattr(g, "clone") else g.copy())
+        with _grad_stream(rt, xin, g):                               # next to the input-gradient convolution below (see trunk_backward)
+            rt.conv_wgrad_bf16(xin, g, out=trainer.grad[name + "/W"])
+            rt.bias_grad(g, out=trainer.grad[name + "/b"])
+            if hasattr(trainer, "_grads_ready"):
+                trainer._grads_ready(name)
+        if name == first:
+            continue                                                  # the image needs no gradient
+        cin, cout = _conv_dims(trainer, name)
+        if gb is None:
+            gb = rtb.bf16_from_nchw(g)
+        below = names[pos - 1] if pos > 0 else None                   # who consumes dL/d(input): a convolution with an input gradient of its own?
+        below_conv = below is not None and below != "pool" and below != first
+        gb, g = rt.conv3x3_bf16_train(gb, trainer.wb_dgrad[name], trainer.zero_bias, cout, cin, relu=False, want_bf16=below_conv, mask=xin)
+    rt.mem.join_aux_stream("grad")
+    return g
+
+
 class _Seg(object):
     def __init__(self, name, shape, offset):
         self.name, self.shape, self.offset = name, tuple(shape), offset
@@ -262,7 +325,11 @@ class RPNTrainer(_BucketedAllReduce):
     def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, comm=None, run_proposal_layer=True, conv_math="mfma"):
         """conv_math: "mfma" = forward and input-gradient convolutions on the fp32 MFMA kernel; "split" = the same fp32 convolutions as
         six bf16 MFMA products of 3-way split operands (csrc/conv_f32s.hip), the 3x3 weight gradients likewise (csrc/train.hip
-        conv_wgrad_f32s_kernel)."""
+        conv_wgrad_f32s_kernel); "bf16" = mixed precision: every product of the 3x3 convolutions' forward, input gradient and weight
+        gradient on bf16 operands (RNE of the fp32 activations, gradients and master weights) with fp32 accumulation -- everything
+        else (bias, ReLU, pools, the RPN heads and losses, the update, the fp32 master weights) as in the fp32 step."""
+        if conv_math not in ("mfma", "split", "bf16"):
+            raise ValueError("RPNTrainer: conv_math must be 'mfma', 'split' or 'bf16', not %r" % (conv_math,))
         self.model, self.rt = model, model.rt
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.comm = comm
@@ -306,6 +373,10 @@ class RPNTrainer(_BucketedAllReduce):
             big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
             self.ws_fwd = {n: rt.mem.empty((3, pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in big}
             self.ws_dgrad = {n: rt.mem.empty((3, pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in big}
+        if conv_math == "bf16":                                       # bf16 weights of the forward / input-gradient convolutions (re-packed every step)
+            pad = rt.bf16_pad
+            self.wb_fwd = {n: rt.mem.empty((pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in self.convs}
+            self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
         self._draw = None
         self.iteration = 0
         self._plan_buckets([n for n, _ in self.convs])       # heads follow rpn_conv_3x3 in the buffer and precede it in time
@@ -346,6 +417,12 @@ class RPNTrainer(_BucketedAllReduce):
             feat, inputs, feat_split = trunk_forward_split(self, x)
             link = rpn.rpn_conv_3x3
             _, mid = rt.conv3x3_f32s_train(feat_split, self.ws_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_split=False)
+        elif self.conv_math == "bf16":
+            # bf16 weights of every forward / input-gradient convolution from the current fp32 master weights: one launch
+            rt.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs])
+            feat, inputs, feat_b = trunk_forward_bf16(self, x)
+            link = rpn.rpn_conv_3x3
+            _, mid = rt.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_bf16=False)
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): one launch
             if _tuning.get("FRCNN_DGRAD_PACK") != "each":          # (=each: A/B hook, one launch per layer inside the backward pass)
@@ -382,7 +459,8 @@ class RPNTrainer(_BucketedAllReduce):
             rt.pack_conv_dgrad_w(rpn._heads_packed[0], 1, out=self.wd_heads)
         g = rt.conv_ex(draw.reshape(1, NP, H, W), self.wd_heads, self.zero_bias, 1, act=2, mask=mid)
         # ---- rpn_conv_3x3, then the trunk in reverse
-        (trunk_backward_split if self.conv_math == "split" else trunk_backward)(self, list(zip(self.layers, inputs)) + [(("rpn_conv_3x3", 0, 0), feat)], g)
+        backward = {"split": trunk_backward_split, "bf16": trunk_backward_bf16}.get(self.conv_math, trunk_backward)
+        backward(self, list(zip(self.layers, inputs)) + [(("rpn_conv_3x3", 0, 0), feat)], g)
         self._dgrad_packed = False
         if self.run_proposal_layer:
             rt.mem.join_side_stream()

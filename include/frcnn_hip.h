@@ -323,6 +323,32 @@ int frcnn_conv3x3_f32s_train(const uint16_t *x, const uint16_t *w_packed, const 
 int frcnn_conv_wgrad_f32s(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* bf16 mixed-precision training forms of the RPN step (RPNTrainer(conv_math="bf16"); train_rpn.py:140-182 with every convolution
+ * product of L.Convolution2D's forward / backward, /root/reference/models/vgg16.py:39-82 and region_proposal_network.py:53, on bf16
+ * operands).  Contract: an operand is RNE(its fp32 value) -- activations, upstream gradients, the fp32 master weights -- and every
+ * product is accumulated in fp32; bias, ReLU, the mask and everything outside the convolutions stay fp32.  Layouts are the 16-bit
+ * chain's: activations [CP/16][H][W][16], weights [CinP/16][tap][CoutP][16] (one part of the split tensors above).
+ * frcnn_bf16_pack_many: the trainers' packed fp32 weights [(ci*9+tap)][co] -> bf16 forward weights and (w_split_dgrad, may be NULL)
+ * input-gradient weights [CoutP/16][tap][CinP][16] (channels swapped, taps rotated 180 degrees), up to 16 layers in ONE launch. */
+typedef frcnn_f32s_pack_desc frcnn_bf16_pack_desc;
+int frcnn_bf16_pack_many(const frcnn_bf16_pack_desc *layers, int n, void *stream);
+/* conv1_1 (Cin <= 3, Cout <= 64): fp32 NCHW image and packed fp32 weights, both rounded in registers -> y_bf16 [CoutP/16][H][W][16]
+ * and (may be NULL) y_nchw (Cout,H,W) fp32; y_bf16 == RNE(y_nchw) bit for bit */
+int frcnn_conv1_bf16_train(const float *x, const float *w_packed_f32, const float *bias, uint16_t *y_bf16, float *y_nchw, int Cin,
+                           int Cout, int H, int W, int relu, void *stream);
+/* 3x3 convolution, blocked bf16 in -> y_bf16 (blocked bf16, may be NULL) and / or y_nchw ((Cout,H,W) fp32, may be NULL); the epilogue
+ * (bias, ReLU, y = (mask > 0) ? y : 0 with mask (Cout,H,W) fp32 or NULL) runs in fp32 and y_bf16 == RNE(y_nchw).  The workspace is
+ * frcnn_conv_f32s_workspace_bytes / _init's (split-K partials behind a counter page zeroed once; every launch leaves it zero); split
+ * pieces are summed in split order (deterministic). */
+int frcnn_conv3x3_bf16_train(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y_bf16, float *y_nchw,
+                             const float *mask, int Cin, int Cout, int H, int W, int relu, void *workspace, size_t workspace_bytes,
+                             void *stream);
+/* 3x3 weight gradient (frcnn_conv_wgrad_f32's arguments and result) on bf16 products: x and dy are the fp32 NCHW tensors, rounded to bf16
+ * inside the kernel; per-split slabs added in a fixed order.  Its workspace: frcnn_conv_wgrad_bf16_workspace_bytes. */
+size_t frcnn_conv_wgrad_bf16_workspace_bytes(int Cin, int Cout, int H, int W);
+int frcnn_conv_wgrad_bf16(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* fully connected layers on split tensors (L.Linear + F.relu, models/faster_rcnn.py:33-36,127-134): x = [3][M][K], w = [3][N][K]
  * bf16 parts (frcnn_f32s_split of the fp32 (M,K) / (N,K) arrays), K % 32 == 0; y = (M,N) fp32, or its three parts [3][M][N] when
  * out_split (the next layer's x).  frcnn_f32s_join: parts -> fp32 (h + m + l, exact). */
