@@ -76,6 +76,16 @@ SIGNATURES = {
     "frcnn_conv3x3_bf16_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_conv_wgrad_bf16_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "frcnn_conv_wgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_f16_pack_many": (_I, [_P, _I, _P]),
+    "frcnn_conv1_f16_train": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "frcnn_conv3x3_f16_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_conv_wgrad_f16_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "frcnn_conv_wgrad_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_loss_scaler_init": (_I, [_P, _F, _P]),
+    "frcnn_scale_by_loss_scale_f32": (_I, [_P, _S, _P, _P]),
+    "frcnn_grad_check_finite_f32": (_I, [_P, _S, _P, _P]),
+    "frcnn_sgd_momentum_wd_scaled": (_I, [_P, _P, _P, _S, _F, _F, _F, _P, _P]),
+    "frcnn_loss_scaler_update": (_I, [_P, _F, _F, _I, _F, _F, _P]),
     "frcnn_f32s_split": (_I, [_P, _S, _P, _P]),
     "frcnn_f32s_join": (_I, [_P, _S, _P, _P]),
     "frcnn_linear_f32s_workspace_bytes": (_S, [_I, _I, _I]),

@@ -655,6 +655,7 @@ conv1_f32s_kernel(const float *__restrict__ x, const float *__restrict__ w, cons
     }
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 // (Cout, Cin, 3, 3) fp32 -> [3 parts][CinP/16][tap][CoutP][16] bf16, zero padded
 __global__ void __launch_bounds__(256)
 pack_w_f32s_kernel(const float *__restrict__ w, int Cout, int Cin, int taps, int CoutP, int CinP, uint16_t *__restrict__ wp) {
@@ -688,6 +689,7 @@ pack_w_f32s_from_packed_kernel(const float *__restrict__ wp, int Cin, int Cout, 
     dst[i] = (uint16_t)h; dst[total + i] = (uint16_t)m; dst[2 * total + i] = (uint16_t)l;
 }
 
+#endif  // !FRCNN_HALF_F16
 // All layers of a trainer in ONE launch (26 launches of 8 us each otherwise, every step): up to 16 layers, each block looks its layer up.
 // NP = 1: the bf16 training step's weights -- only the h term, RNE of the fp32 weight, i.e. frcnn_bf16_pack_conv_w of it
 struct PackManyArgs {
@@ -729,6 +731,7 @@ pack_w_f32s_many_kernel(const PackManyArgs a) {
     }
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 // (C,H,W) fp32 -> [3][CP/16][H*W][16] bf16 parts, channels C..CP-1 zero
 __global__ void __launch_bounds__(256)
 nchw_to_f32s_kernel(const float *__restrict__ x, int C, int HW, int CP, uint16_t *__restrict__ y) {
@@ -766,10 +769,12 @@ f32s_to_nchw_kernel(const uint16_t *__restrict__ x, int C, int HW, int CP, float
     }
 }
 
+#endif  // !FRCNN_HALF_F16
 }  // namespace
 
 extern "C" {
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 int frcnn_f32s_pack_conv_w(const float *w, int Cout, int Cin, uint16_t *w_packed, void *stream) {
     if (!w || !w_packed || Cout < 1 || Cin < 1) return FRCNN_ERR_INVALID;
     const int CoutP = (Cout + 15) / 16 * 16, CinP = (Cin + 15) / 16 * 16;
@@ -786,6 +791,7 @@ int frcnn_f32s_pack_from_packed(const float *w_packed_f32, int Cin, int Cout, in
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 static int pack_many_launch(const frcnn_f32s_pack_desc *layers, int n, bool split, hipStream_t stream) {
     if (!layers || n < 1 || n > 16) return FRCNN_ERR_INVALID;
     PackManyArgs a;
@@ -800,15 +806,21 @@ static int pack_many_launch(const frcnn_f32s_pack_desc *layers, int n, bool spli
         a.block_end[i] = blocks;
     }
     a.n = n;
+#ifndef FRCNN_HALF_F16
     if (split) hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_f32s_many_kernel<kParts>), dim3(blocks), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_f32s_many_kernel<1>), dim3(blocks), dim3(256), 0, stream, a);
+    else
+#endif
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_f32s_many_kernel<1>), dim3(blocks), dim3(256), 0, stream, a);
     return frcnn_launch_status();
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 int frcnn_f32s_pack_many(const frcnn_f32s_pack_desc *layers, int n, void *stream) { return pack_many_launch(layers, n, true, (hipStream_t)stream); }
+#endif  // !FRCNN_HALF_F16
 
 int frcnn_bf16_pack_many(const frcnn_bf16_pack_desc *layers, int n, void *stream) { return pack_many_launch(layers, n, false, (hipStream_t)stream); }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 int frcnn_f32s_from_nchw_f32(const float *x, int C, int H, int W, uint16_t *y, void *stream) {
     if (!x || !y || C < 1 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
     const int CP = (C + 15) / 16 * 16;
@@ -825,6 +837,7 @@ int frcnn_f32s_to_nchw_f32(const uint16_t *x, int C, int H, int W, float *y, voi
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 // persistent first-layer launch: as many workgroups as the chip seats at once (2 per CU for the split form, 4 for the bf16 form, 3
 // for the fp32 form: the kernels' __launch_bounds__), each strides over the tiles
 static int conv1_grid(int ntiles, bool split, int seats = 0) {
@@ -835,6 +848,7 @@ static int conv1_grid(int ntiles, bool split, int seats = 0) {
     return (int)(ntiles < slots ? ntiles : slots);
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 int frcnn_conv1_f32s(const float *x, const float *w, const float *bias, uint16_t *y, int Cin, int Cout, int H, int W, int relu, void *stream) {
     if (!x || !w || !bias || !y || Cin < 1 || Cin > 3 || Cout < 1 || Cout > 64 || H < 1 || W < 1) return FRCNN_ERR_INVALID;
     if ((size_t)H * W * 64 * 2 >= (1ull << 31)) return FRCNN_ERR_INVALID;          // one part of the output behind a 32-bit buffer range
@@ -859,6 +873,7 @@ int frcnn_conv1_f32s_train(const float *x, const float *w_packed_f32, const floa
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 // conv1_1 of the bf16 training step: the first-layer kernel's plain bf16 form (operands RNE-rounded in registers, one MFMA per k-step)
 // on the trainers' packed fp32 weights, y_bf16 = RNE(y_nchw) -- both from the same fp32 epilogue value
 int frcnn_conv1_bf16_train(const float *x, const float *w_packed_f32, const float *bias, uint16_t *y_bf16, float *y_nchw, int Cin, int Cout, int H, int W,
@@ -875,6 +890,7 @@ int frcnn_conv1_bf16_train(const float *x, const float *w_packed_f32, const floa
     return frcnn_launch_status();
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 // conv1_1 of the fp32 chain (frcnn_conv3x3_f32 hands layers with Cin <= 3 and Cout <= 64 over): fp32 NCHW image in, the trainers' packed
 // weights [(ci * 9 + tap)][Cout], fp32 NCHW out, native fp32 MFMA arithmetic
 int frcnn_conv1_f32(const float *x, const float *w_packed, const float *bias, float *y, int Cin, int Cout, int H, int W, int relu, void *stream) {
@@ -897,11 +913,13 @@ int frcnn_conv1_bf16(const float *x, const float *w, const float *bias, uint16_t
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 constexpr size_t kF32sCounterPageBytes = 64 * 1024;
 
 // split-K factor: launches that leave most of the chip's 2 x CUs workgroup slots empty split their K range (FRCNN_F32S_SPLIT overrides)
 constexpr long kF32sMaxSplitTiles = 2048;     // launches with more tiles than this never split
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 // split-K factor: only launches that cannot fill the chip's 2 x CUs workgroup slots ONCE split (160 tiles on 512 slots -> 3).
 // Filling the last partial round of bigger launches the same way (conv3_x: 1216 tiles -> 2 splits, conv4_x: 608 -> 4) measured
 // 5 % faster on conv4_2/3 and 12 % SLOWER on conv3_x / conv4_1 (r02o): a workgroup left alone on its CU runs almost twice as fast,
@@ -990,6 +1008,7 @@ int frcnn_conv3x3_f32s_train(const uint16_t *x, const uint16_t *w_packed, const 
     return conv3x3_f32s_launch(x, w_packed, bias, y_split, y_nchw, mask, Cin, Cout, H, W, relu, 0, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+#endif  // !FRCNN_HALF_F16
 // The bf16 training form: conv_f32s_kernel with ONE operand part (NP = 1).  The stage is 26 KB instead of 74 KB and the registers of
 // two fragment sets are gone, so FOUR workgroups share a CU (kBf16tWps) -- the co-resident workgroups' MFMAs cover each other's staging.
 // Split-K (same workspace and counter-page contract as the split kernel) for launches that cannot fill those slots once.
@@ -1029,13 +1048,16 @@ int frcnn_conv3x3_bf16_train(const uint16_t *x, const uint16_t *w_packed, const 
     return frcnn_launch_status();
 }
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 int frcnn_conv3x3_f32s(const uint16_t *x, const uint16_t *w_packed, const float *bias, void *y, int Cin, int Cout, int H, int W, int relu, int out_mode,
                        void *stream) {
     return frcnn_conv3x3_f32s_ws(x, w_packed, bias, y, Cin, Cout, H, W, relu, out_mode, nullptr, 0, stream);
 }
 
+#endif  // !FRCNN_HALF_F16
 }  // extern "C"
 
+#ifndef FRCNN_HALF_F16   // conv_f32s_f16.hip compiles only the one-part training forms as their fp16 twins
 // ---------------------------------------------------------------------------------------------------
 // Fully connected layers on split tensors: y(M,N) = act(x(M,K) @ W(N,K)^T + b) in fp32, the products as six bf16 MFMAs of the 3-way
 // split operands (L.Linear + F.relu, /root/reference/models/faster_rcnn.py:33-36,127-134).  x and W are [3 parts][rows][K] bf16 (K
@@ -1223,3 +1245,4 @@ int frcnn_linear_f32s(const uint16_t *x, const uint16_t *w, const float *bias, v
 }
 
 }  // extern "C"
+#endif  // !FRCNN_HALF_F16

@@ -33,3 +33,9 @@
 #define frcnn_conv1x1_bf16_splits frcnn_conv1x1_f16_splits
 #define frcnn_im2col7x7s2_bf16 frcnn_im2col7x7s2_f16
 #define frcnn_maxpool3x3s2_bf16 frcnn_maxpool3x3s2_f16
+// the one-part training forms (conv_f32s_f16.hip, train_f16.hip): RPNTrainer(conv_math="f16")
+#define frcnn_conv3x3_bf16_train frcnn_conv3x3_f16_train
+#define frcnn_conv1_bf16_train frcnn_conv1_f16_train
+#define frcnn_bf16_pack_many frcnn_f16_pack_many
+#define frcnn_conv_wgrad_bf16 frcnn_conv_wgrad_f16
+#define frcnn_conv_wgrad_bf16_workspace_bytes frcnn_conv_wgrad_f16_workspace_bytes

@@ -24,6 +24,7 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 
 struct AnchorsD { double a[32][4]; };
 
@@ -370,6 +371,7 @@ pack_dgrad_w_many_kernel(DgradPackArgs a) {
     }
 }
 
+#endif  // !FRCNN_HALF_F16
 // ------------------------------------------------------------------------------------------------
 // Weight gradient of a KS x KS / stride 1 / pad KS/2 convolution on v_mfma_f32_32x32x2_f32:
 //   dWp[(ci*T + tap)][co] = sum over pixels p of x[ci][p + offset(tap)] * dy[co][p]         (T = KS*KS)
@@ -383,6 +385,7 @@ pack_dgrad_w_many_kernel(DgradPackArgs a) {
 // dWp tile to its own slab and wgrad_reduce_kernel adds the slabs in a fixed order (deterministic).
 constexpr int WG_ROWS = 2;
 
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 template <int KS>
 __global__ void __launch_bounds__(256)
 conv_wgrad_mfma_kernel(const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ slabs, int Cin, int Cout, int H, int W,
@@ -763,6 +766,7 @@ conv1_wgrad_kernel(const float *__restrict__ x, const float *__restrict__ dy, fl
     }
 }
 
+#endif  // !FRCNN_HALF_F16
 // The same weight gradient on the bf16 matrix cores with fp32-class results (conv_f32s.hip's scheme: every fp32 value carried as
 // three bf16 terms, six v_mfma_f32_32x32x16_bf16 products per block, fp32 accumulation).  The PIXELS are the reduction axis, so the
 // MFMA's eight consecutive k-values of a lane are eight consecutive pixels of one channel's row: the workgroup reads the fp32 NCHW
@@ -1001,6 +1005,7 @@ wgrad_reduce_kernel(const float *__restrict__ slabs, size_t n, int splits, float
     }
 }
 
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 // WeightDecay hook, then MomentumSGD (Chainer v1): g += wd*W; v = momentum*v - lr*g; W += v
 __global__ void __launch_bounds__(256)
 sgd_momentum_wd_kernel(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ v, size_t n, float lr, float momentum, float wd) {
@@ -1119,6 +1124,7 @@ gather_rows_kernel(const float *__restrict__ src, const int32_t *__restrict__ id
     }
 }
 
+#endif  // !FRCNN_HALF_F16
 struct WgradPlan { int xtiles, nblocks, splits, ci_tiles, co_tiles; size_t slab_floats; };
 
 // The double-buffered 3x3 kernel (one workgroup per CU, half as many slabs) against the single-buffer one (two per CU).  Round 2 measured it
@@ -1168,6 +1174,7 @@ static WgradPlan plan_wgrad(int Cin, int Cout, int H, int W, int ks) {
     return p;
 }
 
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 static AnchorsD load_anchors(const double *anchors_host, int A) {
     AnchorsD anc;
     for (int a = 0; a < 32; ++a)
@@ -1186,10 +1193,12 @@ static AtlLayout atl_layout(int n_all, int G) {
     return L;
 }
 
+#endif  // !FRCNN_HALF_F16
 }  // namespace
 
 extern "C" {
 
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 int frcnn_bbox_overlaps_f64(const double *boxes, int N, const double *query_boxes, int K, double *overlaps, void *stream) {
     if (N < 0 || K < 0 || (N > 0 && K > 0 && (!boxes || !query_boxes || !overlaps))) return FRCNN_ERR_INVALID;
     if (N == 0 || K == 0) return FRCNN_OK;
@@ -1436,6 +1445,7 @@ int frcnn_conv_wgrad_f32s(const float *x, const float *dy, float *dw_packed, int
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 // bf16 form (conv_wgrad_f32s_kernel<1>): one workgroup per CU as the split kernel, but its own plan and workspace size (the split
 // kernel borrows the fp32 kernel's); FRCNN_WGRAD_BF16_SPLITS overrides the pixel splits (at most two per CU)
 static WgradPlan plan_wgrad_bf16(int Cin, int Cout, int H, int W) {
@@ -1474,6 +1484,7 @@ int frcnn_conv_wgrad_bf16(const float *x, const float *dy, float *dw_packed, int
     return frcnn_launch_status();
 }
 
+#ifndef FRCNN_HALF_F16   // train_f16.hip compiles only the one-part weight gradient (conv_wgrad_f32s_kernel<1>) as its fp16 twin
 int frcnn_sgd_momentum_wd(float *w, const float *grad, float *velocity, size_t n, float lr, float momentum, float weight_decay, void *stream) {
     if (n == 0) return FRCNN_OK;
     if (!w || !grad || !velocity) return FRCNN_ERR_INVALID;
@@ -1488,4 +1499,5 @@ int frcnn_transpose_f32(const float *src, int rows, int cols, float *dst, void *
     return frcnn_launch_status();
 }
 
+#endif  // !FRCNN_HALF_F16
 }  // extern "C"

@@ -643,7 +643,8 @@ class Runtime(object):
                                             m.stream()), "frcnn_conv1_f32s_train")
         return ys, yn
 
-    # ------------------------------------------------------------------ bf16 training forms (RPNTrainer(conv_math="bf16"); csrc/conv_f32s.hip, train.hip)
+    # ------------------------------------------------------------------ 16-bit training forms (RPNTrainer(conv_math="bf16" / "f16"); csrc/conv_f32s.hip, train.hip;
+    # called through self.hlib, so with_half("f16") runs the fp16 twins of conv_f32s_f16.hip / train_f16.hip)
     def bf16_pack_many(self, layers):
         """layers: [(packed fp32 weights (cin*9, cout), bf16 fwd weights [CinP/16][9][CoutP][16], bf16 dgrad weights [CoutP/16][9][CinP][16] or None,
         cin, cout)], at most 16: ONE launch; every weight is RNE(fp32)."""
@@ -651,7 +652,7 @@ class Runtime(object):
 
         class Desc(ctypes.Structure):
             _fields_ = [("w", ctypes.c_void_p), ("fwd", ctypes.c_void_p), ("dgr", ctypes.c_void_p), ("cin", ctypes.c_int), ("cout", ctypes.c_int)]
-        m, L = self.mem, self.lib
+        m, L = self.mem, self.hlib
         val = lambda t: None if t is None else m.ptr(t).value
         arr = (Desc * len(layers))(*[Desc(val(w), val(f), val(d), int(ci), int(co)) for (w, f, d, ci, co) in layers])
         _lib.check(L.frcnn_bf16_pack_many(ctypes.cast(arr, ctypes.c_void_p), len(layers), m.stream()), "frcnn_bf16_pack_many")
@@ -659,7 +660,7 @@ class Runtime(object):
     def conv3x3_bf16_train(self, x, w_packed, bias, cin, cout, relu=True, want_bf16=True, want_nchw=True, mask=None):
         """x [CinP/16][H][W][16] bf16 -> (bf16 [CoutP/16][H][W][16] or None, (1,Cout,H,W) fp32 or None); mask (1,Cout,H,W) fp32.
         bf16 products, fp32 accumulation and epilogue; the bf16 output is RNE of the fp32 one."""
-        m, L = self.mem, self.lib
+        m, L, H16 = self.mem, self.lib, self.hlib
         H, W = int(x.shape[1]), int(x.shape[2])
         assert int(x.shape[0]) * 16 == self.bf16_pad(cin) and int(w_packed.shape[0]) * 16 == self.bf16_pad(cin) and (want_bf16 or want_nchw)
         yb = m.empty((self.bf16_pad(cout) // 16, H, W, 16), "i16") if want_bf16 else None
@@ -667,13 +668,13 @@ class Runtime(object):
         ws = self.workspace("conv_f32s", L.frcnn_conv_f32s_workspace_bytes(int(cin), int(cout), H, W),
                             init=lambda w: _lib.check(L.frcnn_conv_f32s_workspace_init(m.ptr(w), w.shape[0], m.stream()),
                                                       "frcnn_conv_f32s_workspace_init"))
-        _lib.check(L.frcnn_conv3x3_bf16_train(m.ptr(x), m.ptr(w_packed), m.ptr(bias), m.ptr(yb), m.ptr(yn), m.ptr(mask), int(cin), int(cout), H, W,
+        _lib.check(H16.frcnn_conv3x3_bf16_train(m.ptr(x), m.ptr(w_packed), m.ptr(bias), m.ptr(yb), m.ptr(yn), m.ptr(mask), int(cin), int(cout), H, W,
                                               int(bool(relu)), m.ptr(ws), ws.shape[0], m.stream()), "frcnn_conv3x3_bf16_train")
         return yb, yn
 
     def conv1_bf16_train(self, x, w_packed_f32, bias, cout, relu=True):
         """First layer, bf16 training form: x (1,Cin<=3,H,W) fp32, packed fp32 weights (cin*9, cout) -> (bf16 blocked, fp32 NCHW)."""
-        m, L = self.mem, self.lib
+        m, L = self.mem, self.hlib
         cin, H, W = [int(v) for v in x.shape[-3:]]
         yb = m.empty((self.bf16_pad(cout) // 16, H, W, 16), "i16")
         yn = m.empty((1, int(cout), H, W), "f32")
@@ -683,7 +684,7 @@ class Runtime(object):
 
     def conv_wgrad_bf16(self, x, dy, out=None):
         """The 3x3 weight gradient on bf16 products of RNE(x), RNE(dy) with fp32 accumulation; same layout as conv_wgrad."""
-        m, L = self.mem, self.lib
+        m, L = self.mem, self.hlib
         ci, H, W = [int(v) for v in x.shape[-3:]]
         co = int(dy.shape[-3])
         dw = out if out is not None else m.empty((ci * 9, co), "f32")
@@ -1093,6 +1094,30 @@ class Runtime(object):
         n = int(np.prod(w.shape))
         _lib.check(L.frcnn_sgd_momentum_wd(m.ptr(w), m.ptr(grad), m.ptr(velocity), n, float(lr), float(momentum), float(weight_decay),
                                            m.stream()), "frcnn_sgd_momentum_wd")
+
+    # ------------------------------------------------------------------ loss scaler of the fp16 step (csrc/loss_scale.hip); `state`: (8,) i32 device words
+    def loss_scaler_init(self, state, init_scale):
+        m, L = self.mem, self.lib
+        _lib.check(L.frcnn_loss_scaler_init(m.ptr(state), float(init_scale), m.stream()), "frcnn_loss_scaler_init")
+
+    def scale_by_loss_scale(self, x, state):
+        m, L = self.mem, self.lib
+        _lib.check(L.frcnn_scale_by_loss_scale_f32(m.ptr(x), int(np.prod(x.shape)), m.ptr(state), m.stream()), "frcnn_scale_by_loss_scale_f32")
+
+    def grad_check_finite(self, g, state):
+        m, L = self.mem, self.lib
+        _lib.check(L.frcnn_grad_check_finite_f32(m.ptr(g), int(np.prod(g.shape)), m.ptr(state), m.stream()), "frcnn_grad_check_finite_f32")
+
+    def sgd_momentum_wd_scaled(self, w, grad, velocity, lr, momentum, weight_decay, state):
+        m, L = self.mem, self.lib
+        n = int(np.prod(w.shape))
+        _lib.check(L.frcnn_sgd_momentum_wd_scaled(m.ptr(w), m.ptr(grad), m.ptr(velocity), n, float(lr), float(momentum), float(weight_decay),
+                                                  m.ptr(state), m.stream()), "frcnn_sgd_momentum_wd_scaled")
+
+    def loss_scaler_update(self, state, growth, backoff, growth_interval, min_scale, max_scale):
+        m, L = self.mem, self.lib
+        _lib.check(L.frcnn_loss_scaler_update(m.ptr(state), float(growth), float(backoff), int(growth_interval), float(min_scale), float(max_scale),
+                                              m.stream()), "frcnn_loss_scaler_update")
 
     def transpose(self, src, out=None):
         m, L = self.mem, self.lib

@@ -62,6 +62,7 @@ def load_npz(path, model):
 
 TRAINER_MODEL = "updater/model:main/"
 TRAINER_OPT = "updater/optimizer:main/"
+TRAINER_SCALER = "updater/loss_scaler/"      # RPNTrainer(conv_math="f16"): scale, good_steps, skipped_steps of its device-side loss scaler
 
 
 def save_trainer_npz(path, trainer):
@@ -76,6 +77,12 @@ def save_trainer_npz(path, trainer):
     d[TRAINER_OPT + "t"] = np.asarray(trainer.iteration, dtype=np.int32)
     d[TRAINER_OPT + "epoch"] = np.asarray(0, dtype=np.int32)
     d["updater/iteration"] = np.asarray(trainer.iteration, dtype=np.int32)
+    scaler = getattr(trainer, "loss_scaler", None)
+    if scaler is not None:             # the fp16 step's loss scaler (no other trainer writes these keys)
+        st = scaler.state()
+        d[TRAINER_SCALER + "scale"] = np.asarray(st["scale"], dtype=np.float32)
+        d[TRAINER_SCALER + "good_steps"] = np.asarray(st["good_steps"], dtype=np.int32)
+        d[TRAINER_SCALER + "skipped_steps"] = np.asarray(st["skipped_steps"], dtype=np.int32)
     with open(path, "wb") as f:
         np.savez(f, **d)
 
@@ -99,4 +106,8 @@ def load_trainer_npz(path, trainer):
     trainer.chainer_layout_to_flat(vel, trainer.V)
     if "updater/iteration" in arrays:
         trainer.iteration = int(arrays["updater/iteration"])
+    scaler = getattr(trainer, "loss_scaler", None)
+    if scaler is not None and TRAINER_SCALER + "scale" in arrays:        # (a snapshot without the keys: the scaler keeps its defaults)
+        scaler.load(float(arrays[TRAINER_SCALER + "scale"]), int(arrays.get(TRAINER_SCALER + "good_steps", 0)),
+                    int(arrays.get(TRAINER_SCALER + "skipped_steps", 0)))
     return trainer

@@ -196,8 +196,8 @@ def trunk_forward_bf16(trainer, x):
     first-layer kernel (fp32 image and weights rounded in registers), the others on csrc/conv_f32s.hip's one-part form.  Every
     convolution leaves its result as fp32 NCHW (what the weight gradient, pooling and the ReLU masks read) and, when a convolution
     follows, as the blocked bf16 tensor RNE(fp32) that one reads.  Pools run on fp32.  -> (feat, inputs, feat_bf16)."""
-    model, rt = trainer.model, trainer.rt
-    rtb = rt.with_half("bf16")
+    model = trainer.model
+    rt = rtb = trainer.rt.with_half(getattr(trainer, "half", "bf16"))      # "f16" (RPNTrainer(conv_math="f16")): the fp16 twins of every 16-bit entry
     layers = model.trunk.layers
     inputs, h, hb = [], x, None
     for idx, l in enumerate(layers):
@@ -221,8 +221,7 @@ def trunk_forward_bf16(trainer, x):
 def trunk_backward_bf16(trainer, layer_inputs, g):
     """trunk_backward_split on bf16 operands: input-gradient convolutions on RNE(upstream gradient) and RNE(rotated weights) with the
     ReLU mask fused, weight gradients on RNE(x), RNE(dy) (csrc/train.hip conv_wgrad_f32s_kernel<1>), bias gradients and pools in fp32."""
-    rt = trainer.rt
-    rtb = rt.with_half("bf16")
+    rt = rtb = trainer.rt.with_half(getattr(trainer, "half", "bf16"))
     first = trainer.convs[0][0]
     names = [l if l == "pool" else l[0] for l, _ in layer_inputs]
     gb = None
@@ -321,15 +320,96 @@ class _BucketedAllReduce(_ParamArena):
             self.comm.all_reduce_sum(self.G)
 
 
+def _is_pow2(v):
+    try:
+        m, _ = np.frexp(float(v))
+    except (TypeError, ValueError):
+        return False
+    return bool(np.isfinite(v)) and float(v) > 0 and m == 0.5
+
+
+class LossScaler(object):
+    """The loss scale of the fp16 step, resident on the device (csrc/loss_scale.hip): scale, overflow flag, skip decision and growth /
+    back-off are words of `self.buf` that the kernels read and write; nothing here synchronises except state().
+    loss_scale: "dynamic" (init_scale, doubled after growth_interval clean steps, halved by every step whose gradients hold an Inf / NaN,
+    clamped to [min_scale, max_scale]) or a power of two (static: an overflowing step is still skipped, the scale never moves).
+    Every constant must be a power of two (scaling is then exact): ValueError otherwise."""
+
+    WORDS = 8
+    DEFAULTS = dict(init_scale=2.0 ** 16, growth=2.0, backoff=0.5, growth_interval=2000, min_scale=1.0, max_scale=2.0 ** 24)
+
+    def __init__(self, rt, loss_scale="dynamic", **constants):
+        unknown = set(constants) - set(self.DEFAULTS)
+        if unknown:
+            raise ValueError("LossScaler: unknown constants %s" % sorted(unknown))
+        c = dict(self.DEFAULTS, **constants)
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError("loss_scale must be 'dynamic' or a power of two, not %r" % (loss_scale,))
+            self.dynamic = True
+        else:
+            if not _is_pow2(loss_scale):
+                raise ValueError("a static loss_scale must be a power of two, not %r" % (loss_scale,))
+            self.dynamic = False
+            s = float(loss_scale)
+            c.update(init_scale=s, growth=1.0, backoff=1.0, min_scale=s, max_scale=s)
+        for k in ("init_scale", "growth", "backoff", "min_scale", "max_scale"):
+            if not _is_pow2(c[k]):
+                raise ValueError("LossScaler: %s must be a power of two, not %r" % (k, c[k]))
+        if c["growth"] < 1 or c["backoff"] > 1 or not c["min_scale"] <= c["init_scale"] <= c["max_scale"] or int(c["growth_interval"]) < 1:
+            raise ValueError("LossScaler: need growth >= 1, backoff <= 1, min_scale <= init_scale <= max_scale, growth_interval >= 1")
+        self.rt, self.c = rt, c
+        self.buf = rt.mem.zeros((self.WORDS,), "i32")
+        rt.loss_scaler_init(self.buf, c["init_scale"])
+
+    def scale(self, x):
+        """x *= S (the gradient of the loss with respect to the heads' outputs)."""
+        self.rt.scale_by_loss_scale(x, self.buf)
+
+    def check(self, g):
+        self.rt.grad_check_finite(g, self.buf)
+
+    def update(self):
+        c = self.c
+        self.rt.loss_scaler_update(self.buf, c["growth"], c["backoff"], c["growth_interval"], c["min_scale"], c["max_scale"])
+
+    def _words(self):
+        w = np.ascontiguousarray(self.rt.mem.to_numpy(self.buf)).astype(np.int32)
+        return w, w.view(np.float32)
+
+    def state(self):
+        """Host copy of the device state (SYNCHRONISES: logs and tests only)."""
+        w, f = self._words()
+        return dict(scale=float(f[0]), good_steps=int(w[2]), found_nonfinite=int(w[3]), skipped_steps=int(w[4]), overflow_steps=int(w[5]),
+                    step_scale=float(f[6]))
+
+    def load(self, scale, good_steps=0, skipped_steps=0):
+        """Resume: scale and counters from a snapshot."""
+        if not _is_pow2(scale):
+            raise ValueError("LossScaler.load: scale must be a power of two, not %r" % (scale,))
+        w = np.zeros((self.WORDS,), np.int32)
+        f = w.view(np.float32)
+        f[0], f[1], f[6] = float(scale), 1.0 / float(scale), float(scale)
+        w[2], w[4] = int(good_steps), int(skipped_steps)
+        self.buf[...] = self.rt.mem.from_numpy(w)
+
+
 class RPNTrainer(_BucketedAllReduce):
-    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, comm=None, run_proposal_layer=True, conv_math="mfma"):
+    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, comm=None, run_proposal_layer=True, conv_math="mfma", loss_scale=None):
         """conv_math: "mfma" = forward and input-gradient convolutions on the fp32 MFMA kernel; "split" = the same fp32 convolutions as
         six bf16 MFMA products of 3-way split operands (csrc/conv_f32s.hip), the 3x3 weight gradients likewise (csrc/train.hip
         conv_wgrad_f32s_kernel); "bf16" = mixed precision: every product of the 3x3 convolutions' forward, input gradient and weight
         gradient on bf16 operands (RNE of the fp32 activations, gradients and master weights) with fp32 accumulation -- everything
-        else (bias, ReLU, pools, the RPN heads and losses, the update, the fp32 master weights) as in the fp32 step."""
-        if conv_math not in ("mfma", "split", "bf16"):
-            raise ValueError("RPNTrainer: conv_math must be 'mfma', 'split' or 'bf16', not %r" % (conv_math,))
+        else (bias, ReLU, pools, the RPN heads and losses, the update, the fp32 master weights) as in the fp32 step; "f16" = the same
+        contract with fp16 operands (three more mantissa bits, |v| <= 65504) plus a loss scale S that lives on the device (LossScaler):
+        the gradient of the loss with respect to the heads' outputs is multiplied by S, so self.G holds S times the gradient until
+        update(), which skips the step when the all-reduced buffer holds an Inf / NaN and otherwise applies G / S.
+        loss_scale (conv_math="f16" only): "dynamic" (the default), a power of two (static), or a dict(loss_scale=..., init_scale=...,
+        growth=..., backoff=..., growth_interval=..., min_scale=..., max_scale=...) of LossScaler's constants."""
+        if conv_math not in ("mfma", "split", "bf16", "f16"):
+            raise ValueError("RPNTrainer: conv_math must be 'mfma', 'split', 'bf16' or 'f16', not %r" % (conv_math,))
+        if loss_scale is not None and conv_math != "f16":
+            raise ValueError("RPNTrainer: loss_scale belongs to conv_math='f16', not %r" % (conv_math,))
         self.model, self.rt = model, model.rt
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.comm = comm
@@ -373,7 +453,13 @@ class RPNTrainer(_BucketedAllReduce):
             big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
             self.ws_fwd = {n: rt.mem.empty((3, pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in big}
             self.ws_dgrad = {n: rt.mem.empty((3, pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in big}
-        if conv_math == "bf16":                                       # bf16 weights of the forward / input-gradient convolutions (re-packed every step)
+        self.half = "f16" if conv_math == "f16" else "bf16"           # the 16-bit operand format of the mixed-precision step
+        self.loss_scaler = None
+        if conv_math == "f16":
+            kw = dict(loss_scale) if isinstance(loss_scale, dict) else {"loss_scale": "dynamic" if loss_scale is None else loss_scale}
+            self.loss_scaler = LossScaler(rt, **kw)
+            self._g_scale_word = 0                                    # which state word holds the scale self.G is multiplied by
+        if conv_math in ("bf16", "f16"):                              # 16-bit weights of the forward / input-gradient convolutions (re-packed every step)
             pad = rt.bf16_pad
             self.wb_fwd = {n: rt.mem.empty((pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in self.convs}
             self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
@@ -417,12 +503,13 @@ class RPNTrainer(_BucketedAllReduce):
             feat, inputs, feat_split = trunk_forward_split(self, x)
             link = rpn.rpn_conv_3x3
             _, mid = rt.conv3x3_f32s_train(feat_split, self.ws_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_split=False)
-        elif self.conv_math == "bf16":
-            # bf16 weights of every forward / input-gradient convolution from the current fp32 master weights: one launch
-            rt.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs])
+        elif self.conv_math in ("bf16", "f16"):
+            # 16-bit weights of every forward / input-gradient convolution from the current fp32 master weights: one launch
+            rth = rt.with_half(self.half)
+            rth.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs])
             feat, inputs, feat_b = trunk_forward_bf16(self, x)
             link = rpn.rpn_conv_3x3
-            _, mid = rt.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_bf16=False)
+            _, mid = rth.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_bf16=False)
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): one launch
             if _tuning.get("FRCNN_DGRAD_PACK") != "each":          # (=each: A/B hook, one launch per layer inside the backward pass)
@@ -450,6 +537,9 @@ class RPNTrainer(_BucketedAllReduce):
         draw = self._draw
         losses, _, _ = rt.rpn_loss(score[0], bbox[0], labels, targets, inds, n_in, A, H, W, rpn._delta, rpn._loss_lambda,
                                    d_score=draw[:2 * A], d_bbox=draw[2 * A:6 * A])
+        if self.loss_scaler is not None:                             # fp16 step: everything below computes S * gradient (the losses are not scaled)
+            self.loss_scaler.scale(draw)
+            self._g_scale_word = 0
         # ---- backward: heads (one 1x1 convolution over the stacked cls|bbox matrix)
         rt.mem.join_aux_stream("grad")                               # the re-packed input-gradient weights are ready
         with _grad_stream(rt, mid, draw):
@@ -459,7 +549,7 @@ class RPNTrainer(_BucketedAllReduce):
             rt.pack_conv_dgrad_w(rpn._heads_packed[0], 1, out=self.wd_heads)
         g = rt.conv_ex(draw.reshape(1, NP, H, W), self.wd_heads, self.zero_bias, 1, act=2, mask=mid)
         # ---- rpn_conv_3x3, then the trunk in reverse
-        backward = {"split": trunk_backward_split, "bf16": trunk_backward_bf16}.get(self.conv_math, trunk_backward)
+        backward = {"split": trunk_backward_split, "bf16": trunk_backward_bf16, "f16": trunk_backward_bf16}.get(self.conv_math, trunk_backward)
         backward(self, list(zip(self.layers, inputs)) + [(("rpn_conv_3x3", 0, 0), feat)], g)
         self._dgrad_packed = False
         if self.run_proposal_layer:
@@ -468,7 +558,14 @@ class RPNTrainer(_BucketedAllReduce):
 
     def update(self):
         self._ensure_adopted()
-        self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
+        if self.loss_scaler is not None:
+            # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
+            self.loss_scaler.check(self.G)
+            self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            self.loss_scaler.update()
+            self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
+        else:
+            self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
         if hasattr(self.model, "mark_params_updated"):
             self.model.mark_params_updated(self)
         self.iteration += 1
@@ -541,8 +638,13 @@ class RPNTrainer(_BucketedAllReduce):
         flat[...] = rt.mem.from_numpy(host)
 
     def grads_chainer_layout(self):
-        """{link path: gradient in Chainer's layout} (host arrays) -- for tests and inspection."""
-        return self.flat_to_chainer_layout(self.G)
+        """{link path: gradient in Chainer's layout} (host arrays) -- for tests and inspection.  An fp16 trainer returns UNSCALED gradients:
+        the raw buffer self.G holds S times the gradient (S = the loss scale of the step that filled it); the division is exact."""
+        out = self.flat_to_chainer_layout(self.G)
+        if self.loss_scaler is not None:
+            s = np.float32(self.loss_scaler._words()[1][self._g_scale_word])
+            out = {k: v / s for k, v in out.items()}
+        return out
 
 
 class RCNNTrainer(_BucketedAllReduce):

@@ -348,6 +348,43 @@ int frcnn_conv3x3_bf16_train(const uint16_t *x, const uint16_t *w_packed, const 
 size_t frcnn_conv_wgrad_bf16_workspace_bytes(int Cin, int Cout, int H, int W);
 int frcnn_conv_wgrad_bf16(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace,
                           size_t workspace_bytes, void *stream);
+/* The fp16 twins of the five entries above (csrc/conv_f32s_f16.hip, train_f16.hip: the same kernel sources compiled with fp16 pack / MFMA):
+ * RPNTrainer(conv_math="f16").  Same signatures, layouts, workspaces and error codes; an operand is RNE-fp16(its fp32 value), so
+ * |v| > 65504 becomes Inf and |v| < 2^-14 is rounded to a multiple of 2^-24 -- the step multiplies its upstream gradient by a loss
+ * scale (below) to keep it above that.  Same reference interface: L.Convolution2D + F.relu and their backward, models/vgg16.py:39-82,
+ * region_proposal_network.py:53. */
+int frcnn_f16_pack_many(const frcnn_bf16_pack_desc *layers, int n, void *stream);
+int frcnn_conv1_f16_train(const float *x, const float *w_packed_f32, const float *bias, uint16_t *y_f16, float *y_nchw, int Cin,
+                          int Cout, int H, int W, int relu, void *stream);
+int frcnn_conv3x3_f16_train(const uint16_t *x, const uint16_t *w_packed, const float *bias, uint16_t *y_f16, float *y_nchw,
+                            const float *mask, int Cin, int Cout, int H, int W, int relu, void *workspace, size_t workspace_bytes,
+                            void *stream);
+size_t frcnn_conv_wgrad_f16_workspace_bytes(int Cin, int Cout, int H, int W);
+int frcnn_conv_wgrad_f16(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
+/* ---- the loss scaler of the fp16 training step (csrc/loss_scale.hip), device-resident: serves the optimizer step of
+ * train_rpn.py:165-174 (MomentumSGD + WeightDecay through the updater) for gradients computed from S * dL/d(head outputs).
+ * `state` is a device buffer of FRCNN_LOSS_SCALER_WORDS 32-bit words:
+ *   [0] scale S (float)   [1] 1 / S (float)   [2] good_steps (int: clean steps since S last changed)   [3] found_nonfinite (int flag)
+ *   [4] skipped_steps (int)   [5] overflow_steps (int: skipped steps that found S already at min_scale)
+ *   [6] step_scale (float: the scale of the last finished step)   [7] reserved
+ * Every scale, growth and back-off factor must be a power of two (FRCNN_ERR_INVALID otherwise): scaling is then exact.
+ * frcnn_scale_by_loss_scale_f32: x *= S.  frcnn_grad_check_finite_f32: sets found_nonfinite when any of g's n values is Inf or NaN
+ *   (one read of g, nothing written otherwise; a flag, so the result does not depend on execution order).
+ * frcnn_sgd_momentum_wd_scaled: frcnn_sgd_momentum_wd on grad * (1 / S) -- bit-identical to that entry on the unscaled gradient -- or,
+ *   when found_nonfinite is set, nothing: w and velocity keep their bits.
+ * frcnn_loss_scaler_update (one wave): found_nonfinite ? (S = max(S * backoff, min_scale), good_steps = 0, skipped_steps += 1)
+ *   : (good_steps += 1; at growth_interval: S = min(S * growth, max_scale), good_steps = 0); clears found_nonfinite.  The host never
+ *   reads the flag.  growth = backoff = 1 and min_scale = max_scale = S give a static scale (overflowing steps are still skipped). */
+#define FRCNN_LOSS_SCALER_WORDS 8
+int frcnn_loss_scaler_init(void *state, float init_scale, void *stream);
+int frcnn_scale_by_loss_scale_f32(float *x, size_t n, const void *state, void *stream);
+int frcnn_grad_check_finite_f32(const float *g, size_t n, void *state, void *stream);
+int frcnn_sgd_momentum_wd_scaled(float *w, const float *grad, float *velocity, size_t n, float lr, float momentum,
+                                 float weight_decay, const void *state, void *stream);
+int frcnn_loss_scaler_update(void *state, float growth, float backoff, int growth_interval, float min_scale, float max_scale,
+                             void *stream);
 
 /* fully connected layers on split tensors (L.Linear + F.relu, models/faster_rcnn.py:33-36,127-134): x = [3][M][K], w = [3][N][K]
  * bf16 parts (frcnn_f32s_split of the fp32 (M,K) / (N,K) arrays), K % 32 == 0; y = (M,N) fp32, or its three parts [3][M][N] when

@@ -1,5 +1,5 @@
 """The 600 x 1000 VGG-16 RPN training step (BASELINE.json configs[4]: synthetic parameters and image, bench.py's ground truth) for
-RPNTrainer(conv_math="mfma" / "split" / "bf16"), interleaved in ONE process over several rounds, one JSON line:
+RPNTrainer(conv_math="mfma" / "split" / "bf16" / "f16"), interleaved in ONE process over several rounds, one JSON line:
 ms/step (median of the rounds), the fwd_bwd / all_reduce / update event times, the fraction of the matching dense peak (fp32 matrix
 157 TF for mfma; split products run on the bf16 pipe at 6 MFMAs per product, so their fp32-equivalent rate is also held against
 2.5 PF / 6; bf16 against the bf16 dense 2.5 PF) -- and the bf16 step's loss and worst gradient distance from the fp32 step on the same
@@ -22,7 +22,7 @@ IM_H, IM_W = 600, 1000
 # 2 x the multiply-adds of the 13 trunk convolutions + rpn_conv_3x3 at 600 x 1000, times three (forward, input gradient, weight gradient;
 # conv1_1 has no input gradient -- counted anyway, it is 0.1 % of the total)
 PEAK = {"mfma": (157.3e12, "fp32 dense (v_mfma_f32_32x32x2_f32)"), "split": (2.5e15 / 6, "bf16 dense 2.5 PF / 6 products"),
-        "bf16": (2.5e15, "bf16 dense 2.5 PF")}
+        "bf16": (2.5e15, "bf16 dense 2.5 PF"), "f16": (2.5e15, "fp16 dense 2.5 PF")}
 
 
 def conv_flops():
@@ -44,7 +44,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--modes", default="mfma,split,bf16")
+    ap.add_argument("--modes", default="mfma,split,bf16,f16")
     args = ap.parse_args()
     import torch
     import chainer_faster_rcnn_amd as pkg
@@ -118,6 +118,10 @@ def main():
                            "conv_fraction_of_peak": round(flops / (med * 1e-3) / PEAK[m][0], 4), "peak": PEAK[m][1]}
         if m in acc:
             res["modes"][m]["accuracy_vs_fp32_step"] = {k: float("%.4g" % v) for k, v in acc[m].items()}
+    if "f16" in ms:                                               # the device-side loss scaler after the timed steps (one synchronising read, here only)
+        res["modes"]["f16"]["loss_scaler"] = trainers["f16"].loss_scaler.state()
+        if "bf16" in ms:
+            res["f16_over_bf16"] = round(res["modes"]["f16"]["ms_per_step"] / res["modes"]["bf16"]["ms_per_step"], 4)
     if "bf16" in ms and "split" in ms:
         res["bf16_over_split"] = round(res["modes"]["bf16"]["ms_per_step"] / res["modes"]["split"]["ms_per_step"], 4)
     print(json.dumps(res))
