@@ -37,6 +37,7 @@ SIGNATURES = {
     "frcnn_roi_pool_fwd_chw_f32s": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
     "frcnn_roi_pool_fwd": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _F, _P, _P, _P, _S, _P]),
     "frcnn_roi_pool_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "frcnn_roi_pool_bwd_ordered": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "frcnn_pack_conv3x3_w": (_I, [_P, _I, _I, _P, _P]),
     "frcnn_conv3x3_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "frcnn_conv3x3_workspace_init": (_I, [_P, _S, _P]),
@@ -81,6 +82,18 @@ SIGNATURES = {
     "frcnn_conv3x3_f16_train": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_conv_wgrad_f16_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "frcnn_conv_wgrad_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_bf16_train_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_bf16_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_dgrad_bf16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_dgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_wgrad_bf16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_wgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_f16_train_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_f16_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_dgrad_f16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_dgrad_f16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
+    "frcnn_linear_wgrad_f16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_linear_wgrad_f16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
     "frcnn_loss_scaler_init": (_I, [_P, _F, _P]),
     "frcnn_scale_by_loss_scale_f32": (_I, [_P, _S, _P, _P]),
     "frcnn_grad_check_finite_f32": (_I, [_P, _S, _P, _P]),

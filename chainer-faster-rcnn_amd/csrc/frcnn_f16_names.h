@@ -39,3 +39,10 @@
 #define frcnn_bf16_pack_many frcnn_f16_pack_many
 #define frcnn_conv_wgrad_bf16 frcnn_conv_wgrad_f16
 #define frcnn_conv_wgrad_bf16_workspace_bytes frcnn_conv_wgrad_f16_workspace_bytes
+// the L.Linear training forms (linear_train_f16.hip): RCNNTrainer(precision="f16")
+#define frcnn_linear_bf16_train frcnn_linear_f16_train
+#define frcnn_linear_bf16_train_workspace_bytes frcnn_linear_f16_train_workspace_bytes
+#define frcnn_linear_dgrad_bf16 frcnn_linear_dgrad_f16
+#define frcnn_linear_dgrad_bf16_workspace_bytes frcnn_linear_dgrad_f16_workspace_bytes
+#define frcnn_linear_wgrad_bf16 frcnn_linear_wgrad_f16
+#define frcnn_linear_wgrad_bf16_workspace_bytes frcnn_linear_wgrad_f16_workspace_bytes

@@ -378,6 +378,15 @@ class Runtime(object):
                    "frcnn_roi_pool_bwd")
         return dx
 
+    def roi_pool_bwd_ordered(self, dy, argmax, C, H, W, out=None):
+        """roi_pool_bwd with every cell summed in RoI order, no atomics (csrc/roi_bwd_ordered.hip): bit-reproducible."""
+        m, L = self.mem, self.lib
+        R, _, outh, outw = [int(v) for v in dy.shape]
+        dx = out if out is not None else m.empty((1, C, H, W), "f32")
+        _lib.check(L.frcnn_roi_pool_bwd_ordered(m.ptr(dy), m.ptr(argmax), R, C, H, W, outh, outw, m.ptr(dx), m.stream()),
+                   "frcnn_roi_pool_bwd_ordered")
+        return dx
+
     # ------------------------------------------------------------------ convolution stack
     def pack_conv3x3_w(self, w):
         m, L = self.mem, self.lib
@@ -691,6 +700,40 @@ class Runtime(object):
         ws = self.workspace("wgrad_bf16", L.frcnn_conv_wgrad_bf16_workspace_bytes(ci, co, H, W))
         _lib.check(L.frcnn_conv_wgrad_bf16(m.ptr(x), m.ptr(dy), m.ptr(dw), ci, co, H, W, m.ptr(ws), ws.shape[0], m.stream()),
                    "frcnn_conv_wgrad_bf16")
+        return dw
+
+    # L.Linear of the mixed-precision stage-2 step (csrc/linear_train_bf16.hip): fp32 arrays in, rounded inside the kernels, fp32 out
+    def linear_bf16_train(self, x, w, bias, relu=False, out=None):
+        """y(M,N) = act(RNE(x)(M,K) RNE(w)(N,K)^T + bias) with fp32 accumulation; bias None: no bias term."""
+        m, L = self.mem, self.hlib
+        M, K = int(x.shape[0]), int(np.prod(x.shape[1:]))
+        N = int(w.shape[0])
+        assert int(w.shape[1]) == K
+        y = out if out is not None else m.empty((M, N), "f32")
+        ws = self.workspace("linear_train", L.frcnn_linear_bf16_train_workspace_bytes(M, N, K))
+        _lib.check(L.frcnn_linear_bf16_train(m.ptr(x), m.ptr(w), m.ptr(bias), m.ptr(y), M, N, K, int(bool(relu)), m.ptr(ws), ws.shape[0], m.stream()),
+                   "frcnn_linear_bf16_train")
+        return y
+
+    def linear_dgrad_bf16(self, dy, w, out=None):
+        """dx(M,K) = RNE(dy)(M,N) RNE(w)(N,K), w read as stored."""
+        m, L = self.mem, self.hlib
+        M, N = int(dy.shape[0]), int(dy.shape[1])
+        K = int(w.shape[1])
+        assert int(w.shape[0]) == N
+        dx = out if out is not None else m.empty((M, K), "f32")
+        ws = self.workspace("linear_train", L.frcnn_linear_dgrad_bf16_workspace_bytes(M, N, K))
+        _lib.check(L.frcnn_linear_dgrad_bf16(m.ptr(dy), m.ptr(w), m.ptr(dx), M, N, K, m.ptr(ws), ws.shape[0], m.stream()), "frcnn_linear_dgrad_bf16")
+        return dx
+
+    def linear_wgrad_bf16(self, dy, x, out=None):
+        """dW(N,K) = RNE(dy)(M,N)^T RNE(x)(M,K), the M rows summed in ascending order."""
+        m, L = self.mem, self.hlib
+        M, N = int(dy.shape[0]), int(dy.shape[1])
+        K = int(np.prod(x.shape[1:]))
+        assert int(x.shape[0]) == M
+        dw = out if out is not None else m.empty((N, K), "f32")
+        _lib.check(L.frcnn_linear_wgrad_bf16(m.ptr(dy), m.ptr(x), m.ptr(dw), M, N, K, None, 0, m.stream()), "frcnn_linear_wgrad_bf16")
         return dw
 
     def conv1_bf16(self, x, w, bias, relu=True):

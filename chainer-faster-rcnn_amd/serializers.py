@@ -62,7 +62,7 @@ def load_npz(path, model):
 
 TRAINER_MODEL = "updater/model:main/"
 TRAINER_OPT = "updater/optimizer:main/"
-TRAINER_SCALER = "updater/loss_scaler/"      # RPNTrainer(conv_math="f16"): scale, good_steps, skipped_steps of its device-side loss scaler
+TRAINER_SCALER = "updater/loss_scaler/"      # RPNTrainer(conv_math="f16") / RCNNTrainer(precision="f16"): scale, good_steps, skipped_steps of the device-side loss scaler
 
 
 def save_trainer_npz(path, trainer):

@@ -660,15 +660,31 @@ class RCNNTrainer(_BucketedAllReduce):
     HEAD = ("fc6", "fc7", "cls_score", "bbox_pred")
 
     def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, dropout_ratio=0.5, comm=None, conv_math="mfma", dropout_rng="numpy",
-                 dropout_seed=0):
+                 dropout_seed=0, precision=None, loss_scale=None):
         """dropout_rng: "numpy" (default) draws both masks on the host from NumPy's global stream exactly as chainer's CPU F.dropout does (two
         np.random.rand calls of n_rois x 4096 values per step: ~7 ms of host time at 300 RoIs, bench.py --mode train-rcnn); "device" draws them
         in the dropout kernel from a counter-based hash of (dropout_seed, step, layer) -- the throughput form, no host work, no H2D.
         conv_math: as in RPNTrainer -- "mfma" = the trunk's forward / input-gradient / weight-gradient convolutions on the fp32 MFMA
-        kernels, "split" = the same fp32 convolutions as six bf16 MFMA products of 3-way split operands (csrc/conv_f32s.hip)."""
+        kernels, "split" = the same fp32 convolutions as six bf16 MFMA products of 3-way split operands (csrc/conv_f32s.hip).
+        precision: None (default: every path above, untouched), "bf16" = mixed precision: EVERY matrix product of the step -- forward, input gradient
+        and weight gradient of the trunk's convolutions, rpn_conv_3x3's forward, forward / dx / dW of the four L.Linear layers -- on RNE-bf16
+        images of the fp32 activations, gradients and master weights, with fp32 accumulation (csrc/conv_f32s.hip, train.hip,
+        linear_train_bf16.hip); everything else (bias, ReLU, pools, the RPN 1x1 heads, proposals, RoI pooling, dropout, losses, the
+        all-reduce, the update on the fp32 master weights) as in the fp32 step; "f16" = the same contract with fp16 operands plus the
+        device-side loss scale of RPNTrainer(conv_math="f16") (LossScaler): rcnn_loss's two gradient outputs are multiplied by S, self.G holds
+        S times the gradient until update(), which skips the step when the all-reduced buffer holds an Inf / NaN.
+        loss_scale (precision="f16" only): "dynamic" (the default), a power of two (static), or a dict of LossScaler's constants."""
         from .models.proposal_target_layer import ProposalTargetLayer
-        assert conv_math in ("mfma", "split")
-        self.conv_math = conv_math
+        if conv_math not in ("mfma", "split"):
+            raise ValueError("RCNNTrainer: conv_math is the arithmetic of the trunk's fp32 convolutions, 'mfma' or 'split', not %r "
+                             "(16-bit operands: precision='bf16' / 'f16')" % (conv_math,))
+        if precision not in (None, "bf16", "f16"):
+            raise ValueError("RCNNTrainer: precision must be None, 'bf16' or 'f16', not %r" % (precision,))
+        if precision is not None and conv_math == "split":
+            raise ValueError("RCNNTrainer: precision=%r replaces the fp32 convolutions; it does not combine with conv_math='split'" % (precision,))
+        if loss_scale is not None and precision != "f16":
+            raise ValueError("RCNNTrainer: loss_scale belongs to precision='f16', not %r" % (precision,))
+        self.conv_math, self.precision = conv_math, precision
         self.model, self.rt = model, model.rt
         self.lr, self.momentum, self.weight_decay, self.dropout_ratio, self.comm = lr, momentum, weight_decay, dropout_ratio, comm
         assert dropout_rng in ("numpy", "device")
@@ -700,6 +716,17 @@ class RCNNTrainer(_BucketedAllReduce):
             big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
             self.ws_fwd = {n: rt.mem.empty((3, pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in big}
             self.ws_dgrad = {n: rt.mem.empty((3, pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in big}
+        self.half = "f16" if precision == "f16" else "bf16"          # the 16-bit operand format of the mixed-precision step
+        self.loss_scaler = None
+        if precision == "f16":
+            kw = dict(loss_scale) if isinstance(loss_scale, dict) else {"loss_scale": "dynamic" if loss_scale is None else loss_scale}
+            self.loss_scaler = LossScaler(rt, **kw)
+            self._g_scale_word = 0                                    # which state word holds the scale self.G is multiplied by
+        if precision is not None:                                     # 16-bit weights of the forward / input-gradient convolutions (re-packed every step)
+            pad = rt.bf16_pad
+            rpn3 = model.RPN.rpn_conv_3x3                             # forward only: stage 2 gives the RPN no gradient
+            self.wb_fwd = {n: rt.mem.empty((pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in self.convs + [("rpn_conv_3x3", rpn3)]}
+            self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
         self.iteration = 0
         # the head (fc6: 411 MB of gradients) is complete before the trunk's backward starts: its bucket rides under all of it
         self._plan_buckets([n for n, _ in self.convs] + list(self.HEAD))
@@ -722,6 +749,16 @@ class RCNNTrainer(_BucketedAllReduce):
         lin = getattr(self.model, name)
         M, K = int(x.shape[0]), int(np.prod(x.shape[1:]))
         N = int(dy.shape[1])
+        keep = getattr(self, "keep_dy", None)
+        if keep is not None and name in keep:                        # tests: the (input, upstream gradient) pair a weight gradient was computed from
+            self.kept_dy[name] = (x.reshape(M, K), dy.clone() if hasattr(dy, "clone") else dy.copy())
+        if self.precision is not None:
+            # 16-bit operands: dW = RNE(dy)^T RNE(x) and dx = RNE(dy) RNE(W) with W read as stored -- fp32 arrays in, rounded inside the kernels
+            # (csrc/linear_train_bf16.hip): no transposed or padded copies of x, W or dW
+            rth = rt.with_half(self.half)
+            rth.linear_wgrad_bf16(dy, x.reshape(M, K), out=self.grad[name + "/W"])
+            rt.bias_grad(rt.transpose(dy).reshape(1, N, 1, M), out=self.grad[name + "/b"])      # db = column sums of dy, as in the fp32 step
+            return rth.linear_dgrad_bf16(dy, lin.W) if need_dx else None
         Mp = (M + 3) // 4 * 4                                        # the GEMM contracts over M here: pad it to a multiple of 4
         if Mp == M:                                                  # (the 128 kept rows of a full sample: nothing to pad, four launches fewer)
             xpad, dpad = x.reshape(M, K), dy
@@ -780,6 +817,12 @@ class RCNNTrainer(_BucketedAllReduce):
             if big:
                 rt.f32s_pack_many([(l.Wp, self.ws_fwd[n], self.ws_dgrad[n], l.cin, l.cout) for n, l in big])
             feat, inputs, _ = trunk_forward_split(self, x)
+        elif self.precision is not None:
+            # 16-bit weights of every forward / input-gradient convolution (rpn_conv_3x3: forward only) from the current fp32 master weights: one launch
+            rth = rt.with_half(self.half)
+            rpn3 = model.RPN.rpn_conv_3x3
+            rth.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs + [("rpn_conv_3x3", rpn3)]])
+            feat, inputs, feat_b = trunk_forward_bf16(self, x)
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): ONE launch on the gradient
             # stream, under the forward pass -- as in RPNTrainer (one launch per layer inside the backward pass was 12 x 17 us on its critical path)
@@ -790,7 +833,11 @@ class RCNNTrainer(_BucketedAllReduce):
             feat, inputs = trunk_forward(model, x, fuse_pools=getattr(self, "keep_dy", None) is None)
         C, H, W = [int(v) for v in feat.shape[1:]]
         stage("trunk_fwd")
-        _, _, prob, bbox = model.RPN.heads(feat, want_score=False, wino=False)      # the training step keeps the direct convolution
+        if self.precision is not None:                                # rpn_conv_3x3 on the blocked 16-bit map, the 1x1 heads in fp32 (as RPNTrainer)
+            _, mid = rth.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], rpn3.b, rpn3.cin, rpn3.cout, relu=True, want_bf16=False)
+            _, prob, bbox = rt.rpn_heads(mid, model.RPN._heads_packed)
+        else:
+            _, _, prob, bbox = model.RPN.heads(feat, want_score=False, wino=False)      # the training step keeps the direct convolution
         rois, _, n_out = model.RPN.proposal_layer.forward_device(prob, bbox, im_h, im_w)      # RPN.train is False in rcnn_train mode
         # ProposalTargetLayer needs the RoIs and the gt boxes only: its float64 IoU matrix is enqueued here and comes back with the RoI count (the
         # one host read the step needs anyway), so the host-side sampling further down overlaps the head's forward pass instead of waiting for it
@@ -812,7 +859,12 @@ class RCNNTrainer(_BucketedAllReduce):
             pool5, argmax = rt.roi_pool_fwd_chw(feat, rois, 7, 7, model._spatial_scale, want_argmax=True)
             stage("roi_pool_fwd")
             pool5 = pool5.reshape(n, -1)
-            a6 = model.fc6(pool5, relu=True)
+            if self.precision is not None:                           # the four L.Linear on RNE(x), RNE(W), fp32 accumulation, bias and ReLU
+                rth = rt.with_half(self.half)
+                fc = lambda lin, xin, relu=False: rth.linear_bf16_train(xin, lin.W, lin.b, relu=relu)
+            else:
+                fc = lambda lin, xin, relu=False: lin(xin, relu=relu)
+            a6 = fc(model.fc6, pool5, relu=True)
             if on_device:                                            # one launch: mask drawn, stored and applied
                 # one counter per FORWARD (two draws each) -- not per update: forward_backward twice without update() must not reuse its masks -- and
                 # the data-parallel rank folded in: every rank draws its own masks from one dropout_seed
@@ -833,14 +885,14 @@ class RCNNTrainer(_BucketedAllReduce):
                     m6 = masks[0]
                 m6 = rt.asarray(m6, "f32")
                 d6 = rt.mul(a6, m6)
-            a7 = model.fc7(d6, relu=True)
+            a7 = fc(model.fc7, d6, relu=True)
             if on_device:
                 d7, m7 = rt.dropout(a7, self.dropout_ratio, (base + 1) & 0xFFFFFFFFFFFFFFFF)
             else:
                 m7 = ((np.random.rand(*a7.shape) >= self.dropout_ratio) * scale).astype(np.float32) if masks is None else masks[1]
                 m7 = rt.asarray(m7, "f32")
                 d7 = rt.mul(a7, m7)
-            cls_score, bbox_pred = model.cls_score(d7), model.bbox_pred(d7)
+            cls_score, bbox_pred = fc(model.cls_score, d7), fc(model.bbox_pred, d7)
             stage("head_fwd")
             return pool5, argmax, a6, d6, m6, a7, d7, m7, cls_score, bbox_pred
 
@@ -874,6 +926,10 @@ class RCNNTrainer(_BucketedAllReduce):
         keep, labels = rt.mem.bitcast(blob[:k], "i32"), rt.mem.bitcast(blob[k:2 * k], "i32")
         ext = blob[2 * k:].reshape(k, -1)
         losses, dcs, dbp = rt.rcnn_loss(rt.gather_rows(cls_score, keep), rt.gather_rows(bbox_pred, keep), labels, ext, model._rcnn_delta)
+        if self.loss_scaler is not None:                             # fp16 step: everything below computes S * gradient (the losses are not scaled)
+            self.loss_scaler.scale(dcs)
+            self.loss_scaler.scale(dbp)
+            self._g_scale_word = 0
         stage("targets_loss")
         # ---- backward: head.  Only the sampled rows carry a gradient (faster_rcnn.py:155-160: the losses see cls_score[keep_inds] and
         # bbox_pred[keep_inds]; get_item's adjoint leaves every other row of the 300 EXACTLY zero), so the four L.Linear backward passes, the
@@ -901,10 +957,14 @@ class RCNNTrainer(_BucketedAllReduce):
         for n_ in reversed(self.HEAD):                             # every head gradient is enqueued: a bucket closed by a head layer starts now
             self._grads_ready(n_)
         # ---- RoI pooling (arg-max scatter) and the trunk; feat = relu(conv5_3): mask before entering conv5_3's backward
-        gfeat = rt.relu_bwd_(rt.roi_pool_bwd(gp.reshape(rows, C, 7, 7), argmaxb.reshape(rows, C, 7, 7), C, H, W), feat)
+        # (16-bit step: this map is rounded for conv5_3's backward products, where the last bit of a cell can decide a rounding -- the scatter with a fixed order
+        # of additions keeps two steps from one state bit-identical; the fp32 step keeps its plane kernel, whose float atomics stay at rounding level)
+        roi_bwd = rt.roi_pool_bwd_ordered if self.precision is not None else rt.roi_pool_bwd
+        gfeat = rt.relu_bwd_(roi_bwd(gp.reshape(rows, C, 7, 7), argmaxb.reshape(rows, C, 7, 7), C, H, W), feat)
         stage("roi_pool_bwd")
         rt.mem.join_aux_stream("grad")                               # the re-packed input-gradient weights are ready
-        (trunk_backward_split if self.conv_math == "split" else trunk_backward)(self, list(zip(self.layers, inputs)), gfeat)
+        backward = trunk_backward_bf16 if self.precision is not None else (trunk_backward_split if self.conv_math == "split" else trunk_backward)
+        backward(self, list(zip(self.layers, inputs)), gfeat)
         self._dgrad_packed = False
         stage("trunk_bwd")
         # rois: the (n, 4) proposals THIS step pooled -- a parity test must hand the oracle these, not the proposals of a second, inference-form forward: the
@@ -916,7 +976,14 @@ class RCNNTrainer(_BucketedAllReduce):
 
     def update(self):
         self._ensure_adopted()
-        self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
+        if self.loss_scaler is not None:
+            # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
+            self.loss_scaler.check(self.G)
+            self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            self.loss_scaler.update()
+            self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
+        else:
+            self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
         if hasattr(self.model, "mark_params_updated"):
             self.model.mark_params_updated(self)
         self.iteration += 1
@@ -962,7 +1029,12 @@ class RCNNTrainer(_BucketedAllReduce):
         flat[...] = rt.mem.from_numpy(host)
 
     def grads_chainer_layout(self):
-        return self.flat_to_chainer_layout(self.G)
+        """{link path: gradient in Chainer's layout} (host arrays).  An fp16 trainer returns UNSCALED gradients (the division by the power-of-two scale is exact)."""
+        out = self.flat_to_chainer_layout(self.G)
+        if self.loss_scaler is not None:
+            s = np.float32(self.loss_scaler._words()[1][self._g_scale_word])
+            out = {k: v / s for k, v in out.items()}
+        return out
 
     def sync_params(self):
         for name, link in self.convs:

@@ -348,6 +348,42 @@ int frcnn_conv3x3_bf16_train(const uint16_t *x, const uint16_t *w_packed, const 
 size_t frcnn_conv_wgrad_bf16_workspace_bytes(int Cin, int Cout, int H, int W);
 int frcnn_conv_wgrad_bf16(const float *x, const float *dy, float *dw_packed, int Cin, int Cout, int H, int W, void *workspace,
                           size_t workspace_bytes, void *stream);
+/* ---- L.Linear in the mixed-precision stage-2 step (csrc/linear_train_bf16.hip; RCNNTrainer(precision="bf16")) -------------------------------------------
+ * Forward, input gradient and weight gradient of L.Linear (+ F.relu) and their backward, models/faster_rcnn.py:33-36,127-134, on bf16 operands with fp32
+ * accumulation.  Every operand is an fp32 array -- x (M,K), W (N,K) as stored, dy (M,N) -- and is rounded to nearest even inside the kernel while it is
+ * staged; outputs are fp32.  M, N and K are ragged (out-of-range reads return 0 through the buffer descriptors); one workgroup holds up to 320 rows, so
+ * the ProposalLayer's 300 rows walk the weights once.  Every tensor behind a 32-bit descriptor: FRCNN_ERR_UNSUPPORTED from 2 GiB.
+ *   frcnn_linear_bf16_train   y(M,N) = act(RNE(x) RNE(W)^T + bias); bias (N) or NULL; split-K slabs in the workspace, added in split order.
+ *   frcnn_linear_dgrad_bf16   dx(M,K) = RNE(dy) RNE(W): W read as stored, transposed in registers on its way into LDS; K % 4 == 0
+ *                             (FRCNN_ERR_UNSUPPORTED otherwise); slabs over N in the workspace, added in split order.
+ *   frcnn_linear_wgrad_bf16   dW(N,K) = RNE(dy)^T RNE(x), summed over the M rows in ascending order, written directly (no slabs: its workspace is
+ *                             0 bytes and may be NULL); K % 4 == 0.
+ * No atomics anywhere: two calls on the same inputs give identical bits.  Tuning key FRCNN_LINEAR_TRAIN_SPLITS (A/B and tests): the number of slabs. */
+size_t frcnn_linear_bf16_train_workspace_bytes(int M, int N, int K);
+int frcnn_linear_bf16_train(const float *x, const float *w, const float *bias, float *y, int M, int N, int K, int relu, void *workspace,
+                            size_t workspace_bytes, void *stream);
+size_t frcnn_linear_dgrad_bf16_workspace_bytes(int M, int N, int K);
+int frcnn_linear_dgrad_bf16(const float *dy, const float *w, float *dx, int M, int N, int K, void *workspace, size_t workspace_bytes,
+                            void *stream);
+size_t frcnn_linear_wgrad_bf16_workspace_bytes(int M, int N, int K);
+int frcnn_linear_wgrad_bf16(const float *dy, const float *x, float *dw, int M, int N, int K, void *workspace, size_t workspace_bytes,
+                            void *stream);
+/* RoI max-pooling backward with a fixed order of additions (csrc/roi_bwd_ordered.hip): frcnn_roi_pool_bwd's arguments and result -- the backward of
+ * F.roi_pooling_2d, call site models/faster_rcnn.py:125-126 -- with every cell's sum taken over the RoIs in ascending order and, within a RoI, the bins in ascending
+ * order (the reference's CPU loop order); no atomics, identical bits from run to run.  The mixed-precision stage-2 step uses it: its result is rounded to 16
+ * bits for conv5_3's backward products.  outh * outw <= 64 and H * W <= 16384 (FRCNN_ERR_UNSUPPORTED beyond). */
+int frcnn_roi_pool_bwd_ordered(const float *dy, const int32_t *argmax, int R, int C, int H, int W, int outh, int outw, float *dx, void *stream);
+/* their fp16 twins (csrc/linear_train_f16.hip: the same source with fp16 pack / MFMA; RCNNTrainer(precision="f16")): same signatures and error codes,
+ * operands RNE-fp16; replaces the same L.Linear forward and backward, models/faster_rcnn.py:33-36,127-134. */
+size_t frcnn_linear_f16_train_workspace_bytes(int M, int N, int K);
+int frcnn_linear_f16_train(const float *x, const float *w, const float *bias, float *y, int M, int N, int K, int relu, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t frcnn_linear_dgrad_f16_workspace_bytes(int M, int N, int K);
+int frcnn_linear_dgrad_f16(const float *dy, const float *w, float *dx, int M, int N, int K, void *workspace, size_t workspace_bytes,
+                           void *stream);
+size_t frcnn_linear_wgrad_f16_workspace_bytes(int M, int N, int K);
+int frcnn_linear_wgrad_f16(const float *dy, const float *x, float *dw, int M, int N, int K, void *workspace, size_t workspace_bytes,
+                           void *stream);
 /* The fp16 twins of the five entries above (csrc/conv_f32s_f16.hip, train_f16.hip: the same kernel sources compiled with fp16 pack / MFMA):
  * RPNTrainer(conv_math="f16").  Same signatures, layouts, workspaces and error codes; an operand is RNE-fp16(its fp32 value), so
  * |v| > 65504 becomes Inf and |v| < 2^-14 is rounded to a multiple of 2^-24 -- the step multiplies its upstream gradient by a loss

@@ -4,7 +4,7 @@
 A kernel whose vmcnt(0) count is of the order of its load count is waiting for its loads one at a time (DESIGN.md section 3.10:
 predicated loads inside unrolled load - use - store loops); the listing under /tmp/isa/<file>.s shows where.
 
-    python scripts/isa_wait_scan.py [min_waits]        # default: kernels with >= 6 full waits
+    python scripts/isa_wait_scan.py [min_waits] [prefix]      # default: kernels with >= 6 full waits; prefix: only csrc files whose name starts with it
 """
 import os
 import re
@@ -15,11 +15,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "chainer-faster-rcnn_amd", "csrc")
 
 
-def main(min_waits=6):
+def main(min_waits=6, prefix=""):
     out_dir = "/tmp/isa"
     os.makedirs(out_dir, exist_ok=True)
     for f in sorted(os.listdir(CSRC)):
-        if not f.endswith(".hip"):
+        if not f.endswith(".hip") or not f.startswith(prefix):
             continue
         asm = os.path.join(out_dir, f[:-4] + ".s")
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
@@ -48,4 +48,4 @@ def main(min_waits=6):
 
 
 if __name__ == "__main__":
-    main(*[int(a) for a in sys.argv[1:]])
+    main(*([int(a) for a in sys.argv[1:2]] + sys.argv[2:3]))
