@@ -111,6 +111,25 @@ def test_round4_kernels_do_not_spill(asm_dir):
                 assert int(re.search(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", meta).group(1)) == lds, frag + ": LDS is not the ring alone"
 
 
+# the Winograd kernel runs two workgroups per CU (__launch_bounds__(256, 2)): two waves per SIMD, so at most 256 registers
+# (VGPRs + AGPRs) per lane and nothing in scratch, and at most half of the CU's 160 KB of LDS each.  All four instantiations the library
+# launches: 8- and 4-channel chunks (cfg 1 / 2), each with the chunk offset in the scalar offset (Cin a whole number of chunks) and with
+# per-chunk descriptors (ragged Cin).  (No row in BOUNDS: the kernel's full waits are its protocol -- one per chunk by design -- not a
+# batched prologue that could come apart.)
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc (cross-compiles without a GPU)")
+def test_winograd_kernel_keeps_two_workgroups_per_cu(asm_dir):
+    text = open(asm_of("conv_wino", asm_dir)).read()
+    found = re.findall(r"\.amdhsa_kernel (\S*conv_wino_f32_kernel\S*)\n(.*?)\.end_amdhsa_kernel", text, re.S)
+    forms = sorted(re.search(r"conv_wino_f32_kernelI(\w+?)EEEv", k).group(1) for k, _ in found)
+    assert forms == ["Li2ELi1ELi4ELi2ELb0", "Li2ELi1ELi4ELi2ELb1", "Li2ELi1ELi8ELi2ELb0", "Li2ELi1ELi8ELi2ELb1"], forms     # <CB, TB, CK, BPC, SOFF>
+    for k, meta in found:
+        field = lambda n: int(re.search(r"\.amdhsa_%s\s+(\d+)" % n, meta).group(1))     # noqa: E731
+        assert field("private_segment_fixed_size") == 0, k + ": scratch in use"
+        assert field("next_free_vgpr") <= 256, "%s: %d registers" % (k, field("next_free_vgpr"))
+        assert field("group_segment_fixed_size") <= 81920, "%s: %d bytes of LDS" % (k, field("group_segment_fixed_size"))
+    assert "scratch_" not in text                                                      # no scratch traffic anywhere in the file's listing
+
+
 # round 5: every DPP read in every kernel of the library sits two wait states behind the VALU write of the register it reads -- checked on the
 # final listing because the compiler's hazard recognizer sees neither a DPP read nor a VALU write inside an inline-asm string (scripts/isa_dpp_scan.py).
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="needs hipcc (cross-compiles without a GPU)")
