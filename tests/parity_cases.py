@@ -492,15 +492,16 @@ def check_linear(rt, M, N, K, relu, seed=0, bias=True):
 
 
 def check_head_decode(rt, R=37, ncls=21, seed=0):
+    from head_loss_cases import assert_same_words, ref_boxes
     rs = np.random.RandomState(seed)
     xy = rs.uniform(0, 500, (R, 2))
     boxes = np.hstack([xy, xy + rs.uniform(16, 400, (R, 2))]).astype(np.float32)
     deltas = (rs.randn(R, 4 * ncls) * 0.3).astype(np.float32)
     score = rs.randn(R, ncls).astype(np.float32) * 3
-    want_boxes = O.clip_boxes(O.bbox_transform_inv(boxes, deltas), np.array([600, 1000]))
+    _, want_boxes = ref_boxes(boxes, deltas, 600, 1000)     # the oracle's restatement with exp evaluated in double and rounded to fp32, as csrc/head.hip does
     want_prob = O.softmax(score, axis=1)
     pb, pp = rt.head_decode(dev(rt, boxes), dev(rt, deltas), dev(rt, score), 600, 1000)
-    assert np.allclose(host(rt, pb), want_boxes, rtol=5e-7, atol=1e-4)
+    assert_same_words(host(rt, pb), want_boxes, "head_decode boxes")         # word for word: operation order, no FMA contraction, that exp
     assert np.allclose(host(rt, pp), want_prob, rtol=1e-5, atol=1e-7)
 
 
@@ -520,9 +521,11 @@ def check_bbox_overlaps(rt, N=500, K=7, seed=0):
     assert np.array_equal(got, O.bbox_overlaps(boxes, q))                      # float64, same operation order: exact
 
 
-def check_anchor_target(rt, fh, fw, im_h, im_w, G, seed=0):
+def check_anchor_target(rt, fh, fw, im_h, im_w, G, seed=0, gt=None):
+    """`gt`: a given (1, G, 5) ground truth in place of the seeded VOC-shaped one (tests/head_loss_cases.py: its edges)"""
     rs = np.random.RandomState(seed)
-    gt = gt_case(rs, G, im_h, im_w)
+    gt = gt_case(rs, G, im_h, im_w) if gt is None else gt
+    assert gt.shape == (1, G, 5) and gt.dtype == np.float32
     info = np.array([[im_h, im_w]], dtype=np.int32)
 
     class NoSubsample(object):          # the device entry point stops before the random subsample
