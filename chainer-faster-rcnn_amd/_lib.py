@@ -99,6 +99,8 @@ SIGNATURES = {
     "frcnn_grad_check_finite_f32": (_I, [_P, _S, _P, _P]),
     "frcnn_sgd_momentum_wd_scaled": (_I, [_P, _P, _P, _S, _F, _F, _F, _P, _P]),
     "frcnn_loss_scaler_update": (_I, [_P, _F, _F, _I, _F, _F, _P]),
+    "frcnn_opt_state_init": (_I, [_P, _I, _D, _D, _P]),
+    "frcnn_opt_step": (_I, [_I, _P, _P, _P, _P, _S, _D, _D, _D, _F, _F, _P, _P, _P]),
     "frcnn_f32s_split": (_I, [_P, _S, _P, _P]),
     "frcnn_f32s_join": (_I, [_P, _S, _P, _P]),
     "frcnn_linear_f32s_workspace_bytes": (_S, [_I, _I, _I]),

@@ -1162,6 +1162,23 @@ class Runtime(object):
         _lib.check(L.frcnn_loss_scaler_update(m.ptr(state), float(growth), float(backoff), int(growth_interval), float(min_scale), float(max_scale),
                                               m.stream()), "frcnn_loss_scaler_update")
 
+    # ------------------------------------------------------------------ Adam / AdaGrad / RMSprop (csrc/optimizer.hip); `opt_state`: (8,) i32 device words
+    OPT_RULES = {"Adam": 1, "AdaGrad": 2, "RMSprop": 3}              # include/frcnn_hip.h FRCNN_OPT_*
+
+    def opt_state_init(self, opt_state, t=0, beta1_pow_t=1.0, beta2_pow_t=1.0):
+        m, L = self.mem, self.lib
+        _lib.check(L.frcnn_opt_state_init(m.ptr(opt_state), int(t), float(beta1_pow_t), float(beta2_pow_t), m.stream()), "frcnn_opt_state_init")
+
+    def opt_step(self, rule, w, grad, state1, state2=None, lr=0.0, beta1=0.0, beta2=0.0, eps=1e-8, weight_decay=0.0, opt_state=None, scaler_state=None):
+        """One update of `rule` ("Adam": lr = alpha; "AdaGrad"; "RMSprop": beta1 = its alpha) over the flat buffers; with scaler_state on
+        grad / S, or nothing at all when that state's overflow flag is set."""
+        m, L = self.mem, self.lib
+        if rule not in self.OPT_RULES:
+            raise ValueError("opt_step: unknown rule %r" % (rule,))
+        n = int(np.prod(w.shape))
+        _lib.check(L.frcnn_opt_step(self.OPT_RULES[rule], m.ptr(w), m.ptr(grad), m.ptr(state1), m.ptr(state2), n, float(lr), float(beta1), float(beta2),
+                                    float(eps), float(weight_decay), m.ptr(opt_state), m.ptr(scaler_state), m.stream()), "frcnn_opt_step")
+
     def transpose(self, src, out=None):
         m, L = self.mem, self.lib
         R, C = int(src.shape[0]), int(src.shape[1])

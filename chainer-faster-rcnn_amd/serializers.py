@@ -4,7 +4,7 @@ keys are chainer link paths -- `trunk/conv1_1/W` (co,ci,3,3), `RPN/rpn_cls_score
 
 `save_trainer_npz` / `load_trainer_npz` cover train_rpn.py:101-105 `extensions.snapshot()`: chainer v1 serialises the trainer as
 `updater/model:main/<link path>` (the parameters), `updater/optimizer:main/<link path>/v` (MomentumSGD's velocity, in the
-parameter's shape), `updater/optimizer:main/t`, `updater/optimizer:main/epoch`, `updater/iteration` [chainer-ext: Trainer.serialize
+parameter's shape; Adam: `/m` and `/v`, AdaGrad: `/h`, RMSprop: `/ms`), `updater/optimizer:main/t`, `updater/optimizer:main/epoch`, `updater/iteration` [chainer-ext: Trainer.serialize
 -> StandardUpdater.serialize -> Optimizer.serialize].  Iterator / extension / trigger entries of such a file are the reference's
 control plane (out of scope): ignored on load, not written on save.
 """
@@ -72,9 +72,16 @@ def save_trainer_npz(path, trainer):
         model.sync_trainers()          # parameters another trainer of the same model owns (the RPN after an rpn -> rcnn alternation)
     trainer.sync_params()
     d = {TRAINER_MODEL + k: rt.mem.to_numpy(rt.mem.contiguous(v)) for k, v in namedparams(model)}
-    for k, v in trainer.flat_to_chainer_layout(trainer.V).items():
-        d[TRAINER_OPT + k + "/v"] = v
-    d[TRAINER_OPT + "t"] = np.asarray(trainer.iteration, dtype=np.int32)
+    for name, arena in trainer.moments.items():        # MomentumSGD: v (velocity); Adam: m, v (second moment); AdaGrad: h; RMSprop: ms
+        for k, v in trainer.flat_to_chainer_layout(arena).items():
+            d[TRAINER_OPT + k + "/" + name] = v
+    t = trainer.iteration
+    if trainer.opt_state is not None:  # Adam: the DEVICE's count of applied steps (an fp16 run's skipped steps are not in it), and its running products
+        st = trainer.opt_state.state()
+        t = st["t"]
+        d[TRAINER_OPT + "beta1_pow_t"] = np.asarray(st["beta1_pow_t"], dtype=np.float64)
+        d[TRAINER_OPT + "beta2_pow_t"] = np.asarray(st["beta2_pow_t"], dtype=np.float64)
+    d[TRAINER_OPT + "t"] = np.asarray(t, dtype=np.int32)
     d[TRAINER_OPT + "epoch"] = np.asarray(0, dtype=np.int32)
     d["updater/iteration"] = np.asarray(trainer.iteration, dtype=np.int32)
     scaler = getattr(trainer, "loss_scaler", None)
@@ -93,6 +100,12 @@ def load_trainer_npz(path, trainer):
     import tempfile
     with np.load(path) as f:
         arrays = {k: f[k] for k in f.files}
+    # the per-parameter state must be the trainer's rule's: `/v` is MomentumSGD's velocity AND Adam's second moment, so a snapshot of
+    # another rule is refused, never half-loaded (a file with no optimizer state at all still resumes a MomentumSGD run from zero velocities)
+    have = set(k.rsplit("/", 1)[1] for k in arrays if k.startswith(TRAINER_OPT) and "/" in k[len(TRAINER_OPT):])
+    want = set(trainer.moments)
+    if have != want and not (trainer.opt == "MomentumSGD" and not have):
+        raise ValueError("load_trainer_npz: the snapshot holds optimizer state %s, a %s trainer needs %s" % (sorted(have), trainer.opt, sorted(want)))
     params = {k[len(TRAINER_MODEL):]: v for k, v in arrays.items() if k.startswith(TRAINER_MODEL)}
     fd, tmp = tempfile.mkstemp(suffix=".npz")
     os.close(fd)
@@ -102,8 +115,16 @@ def load_trainer_npz(path, trainer):
     finally:
         os.remove(tmp)
     trainer._ensure_adopted()
-    vel = {k[len(TRAINER_OPT):-2]: v for k, v in arrays.items() if k.startswith(TRAINER_OPT) and k.endswith("/v")}
-    trainer.chainer_layout_to_flat(vel, trainer.V)
+    for name, arena in trainer.moments.items():
+        sfx = "/" + name
+        trainer.chainer_layout_to_flat({k[len(TRAINER_OPT):-len(sfx)]: v for k, v in arrays.items() if k.startswith(TRAINER_OPT) and k.endswith(sfx)}, arena)
+    if trainer.opt_state is not None:
+        # Adam: t and the running products beta^t go back to the device; a Chainer-written file has t only, and the products are rebuilt
+        # the way the device forms them (t multiplications in double), so the resumed run continues bit for bit
+        t = int(arrays[TRAINER_OPT + "t"]) if TRAINER_OPT + "t" in arrays else 0
+        p1, p2 = (float(arrays[TRAINER_OPT + k]) if TRAINER_OPT + k in arrays else trainer.opt_state.running_power(b, t)
+                  for k, b in (("beta1_pow_t", trainer.beta1), ("beta2_pow_t", trainer.beta2)))
+        trainer.opt_state.load(t, p1, p2)
     if "updater/iteration" in arrays:
         trainer.iteration = int(arrays["updater/iteration"])
     scaler = getattr(trainer, "loss_scaler", None)

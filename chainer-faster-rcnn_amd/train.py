@@ -275,6 +275,80 @@ class _ParamArena(object):
     def _ensure_adopted(self):
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ the update rule (utils/prepare_train.py:146-167 get_optimizer)
+    def _init_optimizer(self, who, opt, opt_args, weight_decay):
+        """Validate `opt` / `opt_args` and set the rule's hyper-parameters as plain attributes (read at every update(), like self.lr)."""
+        if opt not in OPT_DEFAULTS:
+            raise ValueError("%s: opt must be one of %s, not %r" % (who, sorted(OPT_DEFAULTS), opt))
+        args = dict(opt_args or {})
+        unknown = set(args) - set(OPT_DEFAULTS[opt])
+        if unknown:
+            raise ValueError("%s: opt=%r has no hyper-parameter %s (it takes %s)" % (who, opt, sorted(unknown), sorted(OPT_DEFAULTS[opt])))
+        for k, v in dict(OPT_DEFAULTS[opt], **args).items():
+            setattr(self, k, v)
+        if opt != "MomentumSGD" and not float(self.eps) > 0:
+            raise ValueError("%s: eps must be positive (the zero padding of the parameter buffer would compute 0 / 0), not %r" % (who, self.eps))
+        self.opt = opt
+        # train_rpn.py:167 hooks WeightDecay(0.0005) onto MomentumSGD only; an explicit value is honoured by every rule
+        self.weight_decay = (0.0005 if opt == "MomentumSGD" else 0.0) if weight_decay is None else weight_decay
+
+    def _alloc_optimizer_state(self):
+        """The rule's state: one or two zero-initialised arenas in self.W's layout (self.moments: Chainer's state name -> buffer) and, for
+        Adam, the device-resident step count / bias correction (self.opt_state)."""
+        rt = self.rt
+        self.moments = {k: rt.mem.zeros((self.n_flat,), "f32") for k in OPT_STATE_KEYS[self.opt]}
+        self.V = self.moments["v"] if self.opt == "MomentumSGD" else None      # MomentumSGD's velocities
+        self.opt_state = AdamState(rt) if self.opt == "Adam" else None
+
+    def _optimizer_step(self, scaler_state=None):
+        """Adam / AdaGrad / RMSprop over the flat buffers (csrc/optimizer.hip); with a loss scaler's state on G / S, or nothing when its flag is set."""
+        rt, mo = self.rt, self.moments
+        if self.opt == "Adam":
+            rt.opt_step("Adam", self.W, self.G, mo["m"], mo["v"], lr=self.alpha, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                        weight_decay=self.weight_decay, opt_state=self.opt_state.buf, scaler_state=scaler_state)
+        elif self.opt == "AdaGrad":
+            rt.opt_step("AdaGrad", self.W, self.G, mo["h"], lr=self.lr, eps=self.eps, weight_decay=self.weight_decay, scaler_state=scaler_state)
+        else:
+            rt.opt_step("RMSprop", self.W, self.G, mo["ms"], lr=self.lr, beta1=self.alpha, eps=self.eps, weight_decay=self.weight_decay,
+                        scaler_state=scaler_state)
+
+
+# Chainer's defaults (optimizers.Adam / AdaGrad / RMSprop); MomentumSGD's lr and momentum are the trainers' own arguments
+OPT_DEFAULTS = {"MomentumSGD": {}, "Adam": dict(alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8), "AdaGrad": dict(lr=1e-3, eps=1e-8),
+                "RMSprop": dict(lr=1e-2, alpha=0.99, eps=1e-8)}
+# the per-parameter state of each rule under Chainer's names (serializers.py: updater/optimizer:main/<link path>/<name>)
+OPT_STATE_KEYS = {"MomentumSGD": ("v",), "Adam": ("m", "v"), "AdaGrad": ("h",), "RMSprop": ("ms",)}
+
+
+class AdamState(object):
+    """Adam's step count on the device (csrc/optimizer.hip): t = the number of APPLIED steps, the running double products beta1^t and
+    beta2^t, and lr_t.  The update launches read and write them; nothing here synchronises except state()."""
+
+    WORDS = 8
+
+    def __init__(self, rt):
+        self.rt = rt
+        self.buf = rt.mem.zeros((self.WORDS,), "i32")
+        rt.opt_state_init(self.buf)
+
+    def state(self):
+        """Host copy of the device state (SYNCHRONISES: snapshots, logs and tests only)."""
+        w = np.ascontiguousarray(self.rt.mem.to_numpy(self.buf)).astype(np.int32)
+        d = w.view(np.float64)
+        return dict(t=int(w[0]), lr_t=float(w.view(np.float32)[1]), beta1_pow_t=float(d[1]), beta2_pow_t=float(d[2]))
+
+    def load(self, t, beta1_pow_t, beta2_pow_t):
+        """Resume: the step count and the two running products from a snapshot."""
+        self.rt.opt_state_init(self.buf, t, beta1_pow_t, beta2_pow_t)
+
+    @staticmethod
+    def running_power(beta, t):
+        """beta^t as the device forms it: t multiplications in double, starting from 1.0."""
+        p = 1.0
+        for _ in range(int(t)):
+            p = p * float(beta)
+        return p
+
 
 class _BucketedAllReduce(_ParamArena):
     """Data parallel: the gradient all-reduce as a few contiguous TAIL buckets of the flat buffer, each launched asynchronously
@@ -395,7 +469,8 @@ class LossScaler(object):
 
 
 class RPNTrainer(_BucketedAllReduce):
-    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, comm=None, run_proposal_layer=True, conv_math="mfma", loss_scale=None):
+    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=None, comm=None, run_proposal_layer=True, conv_math="mfma", loss_scale=None,
+                 opt="MomentumSGD", opt_args=None):
         """conv_math: "mfma" = forward and input-gradient convolutions on the fp32 MFMA kernel; "split" = the same fp32 convolutions as
         six bf16 MFMA products of 3-way split operands (csrc/conv_f32s.hip), the 3x3 weight gradients likewise (csrc/train.hip
         conv_wgrad_f32s_kernel); "bf16" = mixed precision: every product of the 3x3 convolutions' forward, input gradient and weight
@@ -405,13 +480,18 @@ class RPNTrainer(_BucketedAllReduce):
         the gradient of the loss with respect to the heads' outputs is multiplied by S, so self.G holds S times the gradient until
         update(), which skips the step when the all-reduced buffer holds an Inf / NaN and otherwise applies G / S.
         loss_scale (conv_math="f16" only): "dynamic" (the default), a power of two (static), or a dict(loss_scale=..., init_scale=...,
-        growth=..., backoff=..., growth_interval=..., min_scale=..., max_scale=...) of LossScaler's constants."""
+        growth=..., backoff=..., growth_interval=..., min_scale=..., max_scale=...) of LossScaler's constants.
+        opt: the update rule under the reference's spellings (utils/prepare_train.py:146-167): "MomentumSGD" (lr, momentum: the arguments
+        above), "Adam", "AdaGrad" or "RMSprop", whose hyper-parameters come from opt_args -- dict(alpha, beta1, beta2, eps), dict(lr, eps),
+        dict(lr, alpha, eps); Chainer's defaults otherwise -- and become attributes read at every update() (trainer.alpha *= gamma).
+        weight_decay: None = 0.0005 for MomentumSGD (the reference hooks WeightDecay onto that rule only) and 0 for the others."""
         if conv_math not in ("mfma", "split", "bf16", "f16"):
             raise ValueError("RPNTrainer: conv_math must be 'mfma', 'split', 'bf16' or 'f16', not %r" % (conv_math,))
         if loss_scale is not None and conv_math != "f16":
             raise ValueError("RPNTrainer: loss_scale belongs to conv_math='f16', not %r" % (conv_math,))
         self.model, self.rt = model, model.rt
-        self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
+        self.lr, self.momentum = lr, momentum
+        self._init_optimizer("RPNTrainer", opt, opt_args, weight_decay)      # (AdaGrad / RMSprop: self.lr is the rule's own)
         self.comm = comm
         self.conv_math = conv_math
         self.run_proposal_layer = run_proposal_layer
@@ -441,7 +521,7 @@ class RPNTrainer(_BucketedAllReduce):
         self.n_flat = off
         self.W = rt.mem.zeros((off,), "f32")
         self.G = rt.mem.zeros((off,), "f32")
-        self.V = rt.mem.zeros((off,), "f32")
+        self._alloc_optimizer_state()
         self._ensure_adopted()
         self.grad = {k: rt.mem.view(self.G, s.offset, s.shape) for k, s in self.seg.items()}
         # weights of the input-gradient convolutions (re-packed from the current weights every step)
@@ -561,11 +641,16 @@ class RPNTrainer(_BucketedAllReduce):
         if self.loss_scaler is not None:
             # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
             self.loss_scaler.check(self.G)
-            self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            if self.opt == "MomentumSGD":
+                self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            else:                                                     # (Adam: one more one-lane launch, which counts the step unless it is skipped)
+                self._optimizer_step(self.loss_scaler.buf)
             self.loss_scaler.update()
             self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
-        else:
+        elif self.opt == "MomentumSGD":
             self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
+        else:
+            self._optimizer_step()
         if hasattr(self.model, "mark_params_updated"):
             self.model.mark_params_updated(self)
         self.iteration += 1
@@ -659,8 +744,8 @@ class RCNNTrainer(_BucketedAllReduce):
 
     HEAD = ("fc6", "fc7", "cls_score", "bbox_pred")
 
-    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=0.0005, dropout_ratio=0.5, comm=None, conv_math="mfma", dropout_rng="numpy",
-                 dropout_seed=0, precision=None, loss_scale=None):
+    def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=None, dropout_ratio=0.5, comm=None, conv_math="mfma", dropout_rng="numpy",
+                 dropout_seed=0, precision=None, loss_scale=None, opt="MomentumSGD", opt_args=None):
         """dropout_rng: "numpy" (default) draws both masks on the host from NumPy's global stream exactly as chainer's CPU F.dropout does (two
         np.random.rand calls of n_rois x 4096 values per step: ~7 ms of host time at 300 RoIs, bench.py --mode train-rcnn); "device" draws them
         in the dropout kernel from a counter-based hash of (dropout_seed, step, layer) -- the throughput form, no host work, no H2D.
@@ -673,7 +758,8 @@ class RCNNTrainer(_BucketedAllReduce):
         all-reduce, the update on the fp32 master weights) as in the fp32 step; "f16" = the same contract with fp16 operands plus the
         device-side loss scale of RPNTrainer(conv_math="f16") (LossScaler): rcnn_loss's two gradient outputs are multiplied by S, self.G holds
         S times the gradient until update(), which skips the step when the all-reduced buffer holds an Inf / NaN.
-        loss_scale (precision="f16" only): "dynamic" (the default), a power of two (static), or a dict of LossScaler's constants."""
+        loss_scale (precision="f16" only): "dynamic" (the default), a power of two (static), or a dict of LossScaler's constants.
+        opt, opt_args, weight_decay=None: the update rule and its hyper-parameters, as in RPNTrainer."""
         from .models.proposal_target_layer import ProposalTargetLayer
         if conv_math not in ("mfma", "split"):
             raise ValueError("RCNNTrainer: conv_math is the arithmetic of the trunk's fp32 convolutions, 'mfma' or 'split', not %r "
@@ -686,7 +772,8 @@ class RCNNTrainer(_BucketedAllReduce):
             raise ValueError("RCNNTrainer: loss_scale belongs to precision='f16', not %r" % (precision,))
         self.conv_math, self.precision = conv_math, precision
         self.model, self.rt = model, model.rt
-        self.lr, self.momentum, self.weight_decay, self.dropout_ratio, self.comm = lr, momentum, weight_decay, dropout_ratio, comm
+        self.lr, self.momentum, self.dropout_ratio, self.comm = lr, momentum, dropout_ratio, comm
+        self._init_optimizer("RCNNTrainer", opt, opt_args, weight_decay)
         assert dropout_rng in ("numpy", "device")
         self.dropout_rng, self.dropout_seed = dropout_rng, int(dropout_seed)
         rt = self.rt
@@ -706,7 +793,8 @@ class RCNNTrainer(_BucketedAllReduce):
             add(n + "/W", lin.W.shape)
             add(n + "/b", lin.b.shape)
         self.seg, self.n_flat = segs, off
-        self.W, self.G, self.V = rt.mem.zeros((off,), "f32"), rt.mem.zeros((off,), "f32"), rt.mem.zeros((off,), "f32")
+        self.W, self.G = rt.mem.zeros((off,), "f32"), rt.mem.zeros((off,), "f32")
+        self._alloc_optimizer_state()
         self._ensure_adopted()
         self.grad = {k: rt.mem.view(self.G, sg.offset, sg.shape) for k, sg in segs.items()}
         self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32") for name, link in self.convs[1:]}
@@ -979,11 +1067,16 @@ class RCNNTrainer(_BucketedAllReduce):
         if self.loss_scaler is not None:
             # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
             self.loss_scaler.check(self.G)
-            self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            if self.opt == "MomentumSGD":
+                self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            else:                                                     # (Adam: one more one-lane launch, which counts the step unless it is skipped)
+                self._optimizer_step(self.loss_scaler.buf)
             self.loss_scaler.update()
             self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
-        else:
+        elif self.opt == "MomentumSGD":
             self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
+        else:
+            self._optimizer_step()
         if hasattr(self.model, "mark_params_updated"):
             self.model.mark_params_updated(self)
         self.iteration += 1

@@ -422,6 +422,37 @@ int frcnn_sgd_momentum_wd_scaled(float *w, const float *grad, float *velocity, s
 int frcnn_loss_scaler_update(void *state, float growth, float backoff, int growth_interval, float min_scale, float max_scale,
                              void *stream);
 
+/* ---- the other update rules of utils/prepare_train.py:146-167 (get_optimizer: --opt Adam | AdaGrad | RMSprop; MomentumSGD is
+ * frcnn_sgd_momentum_wd below) over flat fp32 buffers (csrc/optimizer.hip).  Chainer v1's update rules, every operation rounded
+ * separately in fp32 and parenthesised as written (no FMA; correctly rounded `/` and sqrt):
+ *   all rules          ge = g * inv_S + wd * w      (inv_S = word [1] of the loss scaler's state, 1 when scaler_state is NULL; wd may be 0)
+ *   FRCNN_OPT_ADAM     state1 = m, state2 = v; lr = alpha:   m = m + omb1 * (ge - m);  v = v + omb2 * ((ge * ge) - v);
+ *                      w = w - ((lr_t * m) / (sqrt(v) + eps));   omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2),
+ *                      lr_t = (float)(alpha * sqrt(1 - beta2^t) / (1 - beta1^t)) evaluated in double, t = applied steps including this one
+ *   FRCNN_OPT_ADAGRAD  state1 = h (state2, beta1, beta2 ignored):   h = h + (ge * ge);  w = w - (((float)lr * ge) / (sqrt(h) + eps))
+ *   FRCNN_OPT_RMSPROP  state1 = ms, beta1 = RMSprop's alpha (state2, beta2 ignored):   ms = ((float)alpha * ms) + ((oma * ge) * ge);
+ *                      w = w - (((float)lr * ge) / (sqrt(ms) + eps));   oma = (float)(1.0 - alpha)
+ * `opt_state` is a device buffer of FRCNN_OPT_STATE_WORDS 32-bit words, 8-byte aligned, that the host never reads inside a step:
+ *   [0] t (int: applied steps)   [1] lr_t (float: the step size of the last applied Adam step)
+ *   [2..3] beta1^t (double)   [4..5] beta2^t (double)   [6], [7] reserved
+ * The two powers are RUNNING PRODUCTS in double: every applied Adam step does p = p * beta once, starting from 1.0 (no pow()).
+ * frcnn_opt_state_init writes t and the two products (0, 1.0, 1.0 for a fresh run; a resumed run passes what it saved, or rebuilds the
+ * products by t multiplications).  frcnn_opt_step is two launches: one lane advances t (and, for Adam, the products and lr_t), then the
+ * update runs over the n elements.  opt_state is required for Adam; the other rules accept NULL (no prologue launch) or count t in it.
+ * With a scaler_state whose found_nonfinite word is set BOTH launches move nothing: w, the state buffers, t and the products keep their
+ * bits (as frcnn_sgd_momentum_wd_scaled).  Pointers need 4-byte alignment only: 16-byte aligned buffers move as 16-byte vectors, any
+ * other alignment element by element with the same bits.  The update launch is min(ceil(units / 1024), 8 x CUs) workgroups of 256
+ * threads, units = n / 4 vectors or n elements.
+ * FRCNN_ERR_INVALID: an unknown rule; a NULL required pointer; !(eps > 0) (zero-padded arena tails would compute 0 / 0); Adam's beta1 or
+ * beta2, or RMSprop's alpha, outside [0, 1).  n == 0 returns FRCNN_OK. */
+#define FRCNN_OPT_ADAM 1
+#define FRCNN_OPT_ADAGRAD 2
+#define FRCNN_OPT_RMSPROP 3
+#define FRCNN_OPT_STATE_WORDS 8
+int frcnn_opt_state_init(void *opt_state, int t, double beta1_pow_t, double beta2_pow_t, void *stream);
+int frcnn_opt_step(int rule, float *w, const float *grad, float *state1, float *state2, size_t n, double lr, double beta1,
+                   double beta2, float eps, float weight_decay, void *opt_state, const void *scaler_state, void *stream);
+
 /* fully connected layers on split tensors (L.Linear + F.relu, models/faster_rcnn.py:33-36,127-134): x = [3][M][K], w = [3][N][K]
  * bf16 parts (frcnn_f32s_split of the fp32 (M,K) / (N,K) arrays), K % 32 == 0; y = (M,N) fp32, or its three parts [3][M][N] when
  * out_split (the next layer's x).  frcnn_f32s_join: parts -> fp32 (h + m + l, exact). */
