@@ -46,6 +46,9 @@ SIGNATURES = {
     "frcnn_wino_pack_w": (_I, [_P, _I, _I, _I, _P, _P]),
     "frcnn_conv_wino_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "frcnn_conv3x3_wino_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
+    "frcnn_conv_wino_sk_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "frcnn_conv_wino_sk_workspace_init": (_I, [_P, _S, _P]),
+    "frcnn_conv3x3_wino_sk_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_maxpool2x2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_rpn_heads_padded_channels": (_I, [_I]),
     "frcnn_rpn_heads_pack": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),

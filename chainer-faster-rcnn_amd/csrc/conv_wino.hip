@@ -18,6 +18,7 @@
 //     workspace slab and a second launch adds the slabs IN PIECE ORDER, then bias / ReLU / pool: bit-identical over repeats.
 // Weight memory: U holds 16 floats per (cout, cin) pair where the packed direct weights hold 9.
 #include "frcnn_common.h"
+#include <frcnn_sync.h>   // angle brackets: the test emulator shadows these headers via its include path
 #include <frcnn_buffer.h>
 #include <frcnn_intrin.h>
 
@@ -28,45 +29,37 @@ namespace {
 constexpr int kWinoPitch = 40;      // floats per halo row in LDS: ten 16-byte groups x0-4 .. x0+35
 constexpr int kWinoLead = 3;        // halo column 0 (input column x0-1) sits at float 3 of its row
 
-// mode bit 0: ReLU, bit 1: fused 2x2/2 max-pool (ceil mode; ReLU implied), bit 2: K piece -> raw Y (no bias) into y + piece * Cout*H*W
-template <int CB, int TB, int CK, int BPC, bool SOFF>
-__global__ void __launch_bounds__(256, BPC)
-conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
-                     int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, int piece_chunks) {
-    constexpr int NT = 256;
-    constexpr int BCO = 32 * CB;
-    constexpr int HR = 4 * TB + 2;                    // halo rows per channel
-    constexpr int WV = CK * 4 * BCO;                  // float4s of U per chunk: rows (ci, r) x BCO couts (4 k-components each)
-    constexpr int WIT = WV / NT;
-    constexpr int HG = CK * HR * 10;                  // 16-byte halo groups per chunk
-    constexpr int HIT4 = (HG + NT - 1) / NT;
-    constexpr int HVP = (HG + 63) / 64 * 256;         // a buffer holds whole DMA pieces (the tail lanes deposit zeros)
-    constexpr int WBUF = WV * 4;
-    constexpr int ZF = 4 * 2 * TB * CB * 16 * 64;     // epilogue exchange: Z[wave][column][tb][cb][16 regs][64 lanes]
-    constexpr int MAINF = 2 * WBUF + 2 * HVP;
-    constexpr int SMEM = MAINF > ZF ? MAINF : ZF;
+// LDS geometry of one workgroup (4 waves): two U slabs and two halo buffers of a CK-channel chunk; the epilogue's Z exchange reuses them
+template <int CB, int TB, int CK>
+struct WinoGeom {
+    static constexpr int NT = 256;
+    static constexpr int BCO = 32 * CB;
+    static constexpr int HR = 4 * TB + 2;                    // halo rows per channel
+    static constexpr int WV = CK * 4 * BCO;                  // float4s of U per chunk: rows (ci, r) x BCO couts (4 k-components each)
+    static constexpr int WIT = WV / NT;
+    static constexpr int HG = CK * HR * 10;                  // 16-byte halo groups per chunk
+    static constexpr int HIT4 = (HG + NT - 1) / NT;
+    static constexpr int HVP = (HG + 63) / 64 * 256;         // a buffer holds whole DMA pieces (the tail lanes deposit zeros)
+    static constexpr int WBUF = WV * 4;
+    static constexpr int ZF = 4 * 2 * TB * CB * 16 * 64;     // epilogue exchange: Z[wave][column][tb][cb][16 regs][64 lanes]
+    static constexpr int MAINF = 2 * WBUF + 2 * HVP;
+    static constexpr int SMEM = MAINF > ZF ? MAINF : ZF;
     static_assert(WV % NT == 0, "U slab must split into whole per-thread float4s");
     static_assert(CK % 2 == 0 && CK * HR * 3 <= NT, "chunk shape");
     static_assert(SMEM * 4 <= 160 * 1024, "LDS");
-    __shared__ __attribute__((aligned(16))) float smem[SMEM];
+};
 
+// The main loop of one output tile (BCO couts at co0, 4 TB rows at y0, 32 columns at x0) over the K chunks [c_begin, c_end): staging ring,
+// input transform, MFMAs.  acc is zeroed here; the loop's last barrier leaves the staging buffers free for the epilogue.
+template <int CB, int TB, int CK, bool SOFF>
+__device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restrict__ x, const float *__restrict__ u, int Cin, int Cout, int H, int W,
+                                               int x0, int y0, int co0, int c_begin, int c_end, f32x16 (&acc)[TB][4][CB]) {
+    using Geo = WinoGeom<CB, TB, CK>;
+    constexpr int NT = Geo::NT, BCO = Geo::BCO, HR = Geo::HR, WIT = Geo::WIT, HG = Geo::HG, HIT4 = Geo::HIT4, HVP = Geo::HVP, WBUF = Geo::WBUF;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, khalf = lane >> 5;
     const int HW = H * W;
-    const int npx = xtiles * ytiles, ntiles = npx * (Cout / BCO);
-    // XCD-aware placement (as conv.hip): XCD x gets the x-th contiguous eighth of [piece][cout block][pixel tile]
-    int g = blockIdx.x;
-    {
-        const int G = gridDim.x, xcd = g & 7, q = G >> 3, r = G & 7;
-        g = xcd * q + (xcd < r ? xcd : r) + (g >> 3);
-    }
-    const int piece = g / ntiles, tile = g % ntiles;
-    const int pxt = tile % npx, cot = tile / npx;
-    const int tx = pxt % xtiles, ty = pxt / xtiles;
-    const int x0 = tx * 32, y0 = ty * 4 * TB, co0 = cot * BCO;
-    const int c_begin = piece * piece_chunks;
-    const int c_end = nchunks < c_begin + piece_chunks ? nchunks : c_begin + piece_chunks;
     const int K4 = Cin * 4;
 
     const frcnn_buf_t xbuf = frcnn_make_buf(x, (uint32_t)((size_t)Cin * HW * sizeof(float)));
@@ -121,7 +114,6 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
         }
     };
 
-    f32x16 acc[TB][4][CB];
 #pragma unroll
     for (int t = 0; t < TB; ++t)
 #pragma unroll
@@ -189,8 +181,15 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
         cur ^= 1;
     }
 
-    // ---- epilogue.  Z[w][0] = M[w][0] + M[w][1] + M[w][2],  Z[w][1] = M[w][1] - M[w][2] - M[w][3]  (M A, this wave's row)
-    float4 *z4 = reinterpret_cast<float4 *>(smem);          // the loop's last barrier: nobody reads the staging buffers any more
+}
+
+// ---- epilogue, first half.  Z[w][0] = M[w][0] + M[w][1] + M[w][2],  Z[w][1] = M[w][1] - M[w][2] - M[w][3]  (M A, this wave's row), exchanged
+// through LDS (the main loop's last barrier: nobody reads the staging buffers any more)
+template <int CB, int TB>
+__device__ __forceinline__ void wino_z_exchange(float *smem, const f32x16 (&acc)[TB][4][CB]) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    float4 *z4 = reinterpret_cast<float4 *>(smem);
 #pragma unroll
     for (int t = 0; t < TB; ++t)
 #pragma unroll
@@ -208,54 +207,244 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
                 z4[(((wave * 2 + 1) * TB * CB + t * CB + c) * 4 + r4) * 64 + lane] = make_float4(z1[0], z1[1], z1[2], z1[3]);
             }
     __syncthreads();
-    // wave w finishes D registers 4w .. 4w+3 of every accumulator: couts co0 + 32 c + 8 w + 4 khalf + e, all four outputs of the block
+}
+
+// ---- second half: Y = A^T Z.  Wave w finishes D registers 4w .. 4w+3 of every accumulator: couts co0 + 32 c + 8 w + 4 khalf + e, all four
+// outputs of the lane's 2x2 block, for accumulator (t, c)
+template <int CB, int TB>
+__device__ __forceinline__ void wino_y_of_z(const float *smem, int t, int c, float (&yv)[4][2][2]) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float4 *z4 = reinterpret_cast<const float4 *>(smem);
+    float4 zz[4][2];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) zz[r][q] = z4[(((r * 2 + q) * TB * CB + t * CB + c) * 4 + wave) * 64 + lane];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        auto comp = [&](const float4 &v) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); };
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            yv[e][0][q] = (comp(zz[0][q]) + comp(zz[1][q])) + comp(zz[2][q]);
+            yv[e][1][q] = (comp(zz[1][q]) - comp(zz[2][q])) - comp(zz[3][q]);
+        }
+    }
+}
+
+// one 2x2 output block of cout `co` at (oy, ox), inside the map: + bias, ReLU / the fused pool (the block is exactly a pool window), store
+__device__ __forceinline__ void wino_emit(float *__restrict__ y, const float (&yv)[2][2], float b, int co, int oy, int ox, int H, int W, bool relu,
+                                          bool pool, bool has_r, bool has_d, size_t base) {
+    if (pool) {
+        const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+        float m = yv[0][0];
+        if (has_r) m = fmaxf(m, yv[0][1]);
+        if (has_d) m = fmaxf(m, yv[1][0]);
+        if (has_r && has_d) m = fmaxf(m, yv[1][1]);
+        y[(size_t)co * OH * OW + (size_t)(oy >> 1) * OW + (ox >> 1)] = fmaxf(m + b, 0.0f);       // max, +bias, ReLU commute
+    } else {
+        float *yo = y + base + (size_t)co * H * W + (size_t)oy * W + ox;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if ((p && !has_d) || (q && !has_r)) continue;
+                float v = yv[p][q] + b;
+                if (relu) v = fmaxf(v, 0.0f);
+                yo[p * W + q] = v;
+            }
+    }
+}
+
+// mode bit 0: ReLU, bit 1: fused 2x2/2 max-pool (ceil mode; ReLU implied), bit 2: K piece -> raw Y (no bias) into y + piece * Cout*H*W
+template <int CB, int TB, int CK, int BPC, bool SOFF>
+__global__ void __launch_bounds__(256, BPC)
+conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                     int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, int piece_chunks) {
+    using Geo = WinoGeom<CB, TB, CK>;
+    constexpr int BCO = Geo::BCO;
+    __shared__ __attribute__((aligned(16))) float smem[Geo::SMEM];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, khalf = lane >> 5;
+    const int HW = H * W;
+    const int npx = xtiles * ytiles, ntiles = npx * (Cout / BCO);
+    // XCD-aware placement (as conv.hip): XCD x gets the x-th contiguous eighth of [piece][cout block][pixel tile]
+    int g = blockIdx.x;
+    {
+        const int G = gridDim.x, xcd = g & 7, q = G >> 3, r = G & 7;
+        g = xcd * q + (xcd < r ? xcd : r) + (g >> 3);
+    }
+    const int piece = g / ntiles, tile = g % ntiles;
+    const int pxt = tile % npx, cot = tile / npx;
+    const int tx = pxt % xtiles, ty = pxt / xtiles;
+    const int x0 = tx * 32, y0 = ty * 4 * TB, co0 = cot * BCO;
+    const int c_begin = piece * piece_chunks;
+    const int c_end = nchunks < c_begin + piece_chunks ? nchunks : c_begin + piece_chunks;
+
+    f32x16 acc[TB][4][CB];
+    wino_tile_loop<CB, TB, CK, SOFF>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+    wino_z_exchange<CB, TB>(smem, acc);
     const bool relu = (mode & 1) != 0, pool = (mode & 2) != 0, partial = (mode & 4) != 0;
-    const int OH = (H + 1) / 2, OW = (W + 1) / 2;
+    const int tr = l31 >> 4, tc = l31 & 15;
 #pragma unroll
     for (int t = 0; t < TB; ++t) {
         const int oy = y0 + 4 * t + 2 * tr, ox = x0 + 2 * tc;
         const bool in0 = oy < H && ox < W, has_r = ox + 1 < W, has_d = oy + 1 < H;
 #pragma unroll
         for (int c = 0; c < CB; ++c) {
-            float4 zz[4][2];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) zz[r][q] = z4[(((r * 2 + q) * TB * CB + t * CB + c) * 4 + wave) * 64 + lane];
+            float yv[4][2][2];
+            wino_y_of_z<CB, TB>(smem, t, c, yv);
             const int cob = co0 + 32 * c + 8 * wave + 4 * khalf;
             const float4 bq = partial ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(&bias[cob]);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                auto comp = [&](const float4 &v) { return e == 0 ? v.x : (e == 1 ? v.y : (e == 2 ? v.z : v.w)); };
-                float yv[2][2];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    yv[0][q] = (comp(zz[0][q]) + comp(zz[1][q])) + comp(zz[2][q]);
-                    yv[1][q] = (comp(zz[1][q]) - comp(zz[2][q])) - comp(zz[3][q]);
-                }
-                const float b = comp(bq);
-                const int co = cob + e;
+                const float b = e == 0 ? bq.x : (e == 1 ? bq.y : (e == 2 ? bq.z : bq.w));
                 if (!in0) continue;
-                if (pool) {
-                    float m = yv[0][0];
-                    if (has_r) m = fmaxf(m, yv[0][1]);
-                    if (has_d) m = fmaxf(m, yv[1][0]);
-                    if (has_r && has_d) m = fmaxf(m, yv[1][1]);
-                    y[(size_t)co * OH * OW + (size_t)(oy >> 1) * OW + (ox >> 1)] = fmaxf(m + b, 0.0f);       // max, +bias, ReLU commute
-                } else {
-                    float *yo = y + (partial ? (size_t)piece * Cout * HW : 0) + (size_t)co * HW + (size_t)oy * W + ox;
+                wino_emit(y, yv[e], b, cob + e, oy, ox, H, W, relu, pool, has_r, has_d, partial ? (size_t)piece * Cout * HW : 0);
+            }
+        }
+    }
+}
+
+// ---- the form that finishes its K split itself (frcnn_conv3x3_wino_sk_f32).  Work distribution as conv.hip's stream-K: the unit is one
+// 8-channel chunk of one output tile, total = ntiles * nchunks units, workgroup g of G takes the contiguous range [g*total/G, (g+1)*total/G)
+// -- or, with pieces > 0 (FRCNN_CONV_WINO_SK_PIECES), the classic launch's partition: tile g / pieces, its chunks
+// [p * piece_chunks, (p+1) * piece_chunks) for p = g % pieces.  A workgroup may end one tile, own whole tiles and begin another; the staging
+// ring restarts at every tile boundary.  A tile that one workgroup owns whole takes the normal epilogue and touches no workspace.  A piece
+// of a shared tile runs the output transform and stores its raw Y lane-linear (8 float4 per thread: 64 couts x 4 x 32 floats = 32 KB) in
+// one of its workgroup's two slots (0: the piece it starts with, 1: the piece it ends with) as write-through 16-byte stores, drains,
+// barriers and takes a ticket on the tile's counter; the holder of ticket P-1 acquires, puts the counter back to zero and adds the P
+// pieces in ascending piece order (s = y_0; s += y_k, wino_combine_kernel's order), then bias / ReLU / pool through the same code as the
+// main epilogue.  Nobody waits for anybody: correctness does not depend on residency or arrival order.
+template <bool SOFF>
+__global__ void __launch_bounds__(256, 2)
+wino_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                   int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, long long total, int pieces, int piece_chunks,
+                   float *__restrict__ slots, int *__restrict__ tile_counters) {
+    constexpr int CB = 2, TB = 1, CK = 8;
+    using Geo = WinoGeom<CB, TB, CK>;
+    constexpr int BCO = Geo::BCO, NT = Geo::NT;
+    constexpr int SLOT_V = TB * CB * 4;                      // float4s per thread and slot
+    constexpr size_t kSlotFloats = (size_t)NT * SLOT_V * 4;
+    __shared__ __attribute__((aligned(16))) float smem[Geo::SMEM];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, khalf = lane >> 5;
+    const int tr = l31 >> 4, tc = l31 & 15;
+    const int npx = xtiles * ytiles;
+    // XCD-aware placement: XCD x gets the x-th contiguous eighth of the ranges, so the ranges of one cout block meet its slice of U in one L2
+    const long long G = gridDim.x;
+    long long g = blockIdx.x;
+    {
+        const long long xcd = g & 7, q = G >> 3, r = G & 7;
+        g = xcd * q + (xcd < r ? xcd : r) + (g >> 3);
+    }
+    auto start_of = [&](long long b) -> long long {          // first unit of workgroup b's range (b == G: total)
+        if (pieces > 0) {
+            const long long c = (b % pieces) * (long long)piece_chunks;
+            return (b / pieces) * nchunks + (c < nchunks ? c : nchunks);
+        }
+        return b * total / G;
+    };
+    auto owner_of = [&](long long i) -> long long {          // the workgroup whose range contains unit i
+        if (pieces > 0) return (i / nchunks) * pieces + (i % nchunks) / piece_chunks;
+        long long b = i * G / total;
+        while (start_of(b + 1) <= i) ++b;
+        while (start_of(b) > i) --b;
+        return b;
+    };
+    const long long it_begin = start_of(g), it_end = start_of(g + 1);
+    const bool relu = (mode & 1) != 0, pool = (mode & 2) != 0;
+
+    for (long long it = it_begin; it < it_end;) {
+        const int tile = (int)(it / nchunks);
+        const int c_begin = (int)(it - (long long)tile * nchunks);
+        const int c_end = (int)((long long)nchunks < c_begin + (it_end - it) ? (long long)nchunks : c_begin + (it_end - it));
+        const int pxt = tile % npx, cot = tile / npx;
+        const int x0 = (pxt % xtiles) * 32, y0 = (pxt / xtiles) * 4 * TB, co0 = cot * BCO;
+        if (it != it_begin) __syncthreads();                 // the previous tile's epilogue is done with the LDS the ring restarts in
+
+        f32x16 acc[TB][4][CB];
+        wino_tile_loop<CB, TB, CK, SOFF>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+        wino_z_exchange<CB, TB>(smem, acc);
+
+        const bool whole = c_begin == 0 && c_end == nchunks;
+        float4 sum[SLOT_V];                                  // raw Y of this thread's 2x2 blocks: [t][c][e] x (y00, y01, y10, y11)
 #pragma unroll
-                    for (int p = 0; p < 2; ++p)
+        for (int t = 0; t < TB; ++t)
 #pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            if ((p && !has_d) || (q && !has_r)) continue;
-                            float v = yv[p][q] + b;
-                            if (relu) v = fmaxf(v, 0.0f);
-                            yo[p * W + q] = v;
-                        }
+            for (int c = 0; c < CB; ++c) {
+                float yv[4][2][2];
+                wino_y_of_z<CB, TB>(smem, t, c, yv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sum[(t * CB + c) * 4 + e] = make_float4(yv[e][0][0], yv[e][0][1], yv[e][1][0], yv[e][1][1]);
+            }
+        bool finish = true;
+        if (!whole) {
+            const long long t_first = (long long)tile * nchunks;
+            const long long g_first = owner_of(t_first), g_last = owner_of(t_first + nchunks - 1);
+            const int P = (int)(g_last - g_first + 1);
+            const int my_slot = (it == it_begin) ? 0 : 1;
+            const frcnn_buf_t pbuf = frcnn_make_buf(slots + ((size_t)g * 2 + my_slot) * kSlotFloats, (uint32_t)(kSlotFloats * sizeof(float)));
+#pragma unroll
+            for (int v = 0; v < SLOT_V; ++v)                 // + 0.0f: the classic pieces store Y + a zero bias (a -0 becomes +0 there too)
+                frcnn_buf_store_f32x4_wt(pbuf, (uint32_t)((v * NT + tid) * 16),
+                                         make_float4(sum[v].x + 0.0f, sum[v].y + 0.0f, sum[v].z + 0.0f, sum[v].w + 0.0f));
+            // write-through stores need no release fence: every wave drains, barrier, one ticket (cdna_hip_programming.md G16 R1)
+            frcnn_drain_vmem();
+            __syncthreads();                                 // ... and everybody has read its Z: the ticket travels through smem[0]
+            int *s_ticket = reinterpret_cast<int *>(smem);
+            if (tid == 0) *s_ticket = frcnn_ticket(&tile_counters[tile]);
+            __syncthreads();
+            finish = (*s_ticket == P - 1);                   // workgroup-uniform
+            if (finish) {
+                if (tid == 0) {
+                    frcnn_acquire_agent();
+                    frcnn_counter_reset(&tile_counters[tile]);      // all P tickets are drawn: the page is zero again for the next launch
+                }
+                __syncthreads();
+                // ALL P pieces in piece order, this workgroup's own one read back from its slot: the sum does not depend on who arrived last
+                for (int q = 0; q < P; ++q) {
+                    const long long b = g_first + q;
+                    const int slot = (q == 0 && start_of(b) != t_first) ? 1 : 0;
+                    const float4 *piece = reinterpret_cast<const float4 *>(slots + ((size_t)b * 2 + slot) * kSlotFloats);
+                    float4 v[SLOT_V];
+#pragma unroll
+                    for (int e = 0; e < SLOT_V; ++e) v[e] = piece[(size_t)e * NT + tid];       // all loads of a piece in flight
+#pragma unroll
+                    for (int e = 0; e < SLOT_V; ++e) frcnn_pin(v[e]);
+#pragma unroll
+                    for (int e = 0; e < SLOT_V; ++e) {
+                        if (q == 0) sum[e] = v[e];
+                        else { sum[e].x += v[e].x; sum[e].y += v[e].y; sum[e].z += v[e].z; sum[e].w += v[e].w; }
+                    }
                 }
             }
         }
+        if (finish) {
+#pragma unroll
+            for (int t = 0; t < TB; ++t) {
+                const int oy = y0 + 4 * t + 2 * tr, ox = x0 + 2 * tc;
+                const bool in0 = oy < H && ox < W, has_r = ox + 1 < W, has_d = oy + 1 < H;
+#pragma unroll
+                for (int c = 0; c < CB; ++c) {
+                    const int cob = co0 + 32 * c + 8 * wave + 4 * khalf;
+                    const float4 bq = *reinterpret_cast<const float4 *>(&bias[cob]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float b = e == 0 ? bq.x : (e == 1 ? bq.y : (e == 2 ? bq.z : bq.w));
+                        const float4 sv = sum[(t * CB + c) * 4 + e];
+                        const float yv[2][2] = {{sv.x, sv.y}, {sv.z, sv.w}};
+                        if (!in0) continue;
+                        wino_emit(y, yv, b, cob + e, oy, ox, H, W, relu, pool, has_r, has_d, 0);
+                    }
+                }
+            }
+        }
+        it += c_end - c_begin;
     }
 }
 
@@ -373,6 +562,49 @@ static int pick_wino_pieces(int cfg, int Cin, int Cout, int H, int W) {
     return pieces < maxp ? pieces : maxp;
 }
 
+
+// ---- the in-kernel form: plan, pick, launch
+constexpr size_t kWinoSkCounterPage = 64 * 1024;               // one int per tile; zeroed once, every launch leaves it zero
+constexpr size_t kWinoSkSlotBytes = 64 * 4 * 32 * sizeof(float);
+
+struct WinoSkPlan { WinoPlan t; long long total; int G, pieces; bool classic, shared, self_cleaning; size_t counters_bytes, ws_bytes; };
+
+// Which shapes take the in-kernel form (profiles/wino_sk_gate.txt): those the classic launch splits (fewer tiles than two rounds of the
+// chip's 2 x CU workgroup slots, K long enough to split) -- with the classic launch's pieces by default, with one contiguous range per
+// slot (G = min(total, 2 x CU count)) under FRCNN_CONV_WINO_SK_BALANCE=1.  Everything else keeps the classic whole-tile launch.  FRCNN_CONV_WINO_SK_G / FRCNN_CONV_WINO_SK_PIECES force the form and its partition on any shape
+// (FRCNN_CONV_WINO_SK_PIECES=-1: on the shapes the classic launch splits, with its piece count).
+static WinoSkPlan plan_wino_sk(int Cin, int Cout, int H, int W) {
+    WinoSkPlan p;
+    const int forced_g = frcnn_tune_int("FRCNN_CONV_WINO_SK_G", 0);
+    int forced_p = frcnn_tune_int("FRCNN_CONV_WINO_SK_PIECES", 0);
+    const int classic_pieces = pick_wino_pieces(1, Cin, Cout, H, W);
+    if (forced_p < 0) forced_p = classic_pieces > 1 ? classic_pieces : 0;      // -1: the classic rule's own count per shape (an unsplit shape stays classic)
+    // The adopted partition is the classic launch's own (bit-identical outputs: the proposals' coordinates feel every regrouping of the K sum
+    // in their last bits); FRCNN_CONV_WINO_SK_BALANCE=1 takes one balanced range per workgroup slot instead (faster: profiles/wino_sk_gate.txt)
+    const bool balance = frcnn_tune_int("FRCNN_CONV_WINO_SK_BALANCE", 0) == 1;
+    if (forced_p == 0 && forced_g <= 0 && !balance && classic_pieces > 1) forced_p = classic_pieces;
+    p.t = plan_wino<2, 1, 8>(Cin, Cout, H, W, forced_p > 0 ? forced_p : 1);
+    p.total = (long long)p.t.ntiles * p.t.nchunks;
+    p.classic = false;
+    p.pieces = 0;
+    if (forced_p > 0) {
+        p.pieces = p.t.pieces;
+        p.G = p.t.ntiles * p.t.pieces;
+        p.shared = p.t.pieces > 1;
+    } else {
+        const long long slots = 2LL * frcnn_cu_count();
+        if (forced_g > 0) p.G = (int)(forced_g < p.total ? forced_g : p.total);
+        else if (classic_pieces > 1) p.G = (int)(slots < p.total ? slots : p.total);
+        else { p.G = p.t.ntiles; p.classic = true; }
+        p.shared = p.G != p.t.ntiles;
+    }
+    const size_t need = frcnn_align256((size_t)p.t.ntiles * sizeof(int));
+    p.counters_bytes = need > kWinoSkCounterPage ? need : kWinoSkCounterPage;
+    p.self_cleaning = need <= kWinoSkCounterPage;               // more than 16384 tiles: the counters are zeroed per launch instead
+    p.ws_bytes = p.shared ? p.counters_bytes + (size_t)p.G * 2 * kWinoSkSlotBytes : 0;
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -413,6 +645,41 @@ int frcnn_conv3x3_wino_f32(const float *x, const float *u, const float *bias, fl
         case 2: return launch_wino<2, 1, 4, 2>(x, u, bias, y, Cin, Cout, H, W, mode, pieces, workspace, workspace_bytes, stream);
         default: return launch_wino<2, 1, 8, 2>(x, u, bias, y, Cin, Cout, H, W, mode, pieces, workspace, workspace_bytes, stream);
     }
+}
+
+size_t frcnn_conv_wino_sk_workspace_bytes(int Cin, int Cout, int H, int W) {
+    if (Cin < 1 || Cout < 1 || H < 1 || W < 1 || (Cout % 64) != 0) return 0;
+    const WinoSkPlan p = plan_wino_sk(Cin, Cout, H, W);
+    return p.ws_bytes > kWinoSkCounterPage ? p.ws_bytes : kWinoSkCounterPage;
+}
+
+int frcnn_conv_wino_sk_workspace_init(void *workspace, size_t workspace_bytes, void *stream) {
+    if (!workspace || workspace_bytes < kWinoSkCounterPage) return FRCNN_ERR_INVALID;
+    FRCNN_HIP_TRY(hipMemsetAsync(workspace, 0, kWinoSkCounterPage, (hipStream_t)stream));
+    return FRCNN_OK;
+}
+
+// the arguments of frcnn_conv3x3_wino_f32; shapes that share no tile (plan_wino_sk) need no workspace and take the classic launch
+int frcnn_conv3x3_wino_sk_f32(const float *x, const float *u, const float *bias, float *y, int Cin, int Cout, int H, int W, int act,
+                              void *workspace, size_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!x || !u || !bias || !y || Cin < 1 || Cout < 1 || H < 1 || W < 1 || (Cout % 64) != 0) return FRCNN_ERR_INVALID;
+    if (act != 0 && act != 1 && act != 4) return FRCNN_ERR_INVALID;
+    if ((size_t)Cin * H * W * 4 >= (1ull << 31) || (size_t)Cin * 16 * Cout * 4 >= (1ull << 31)) return FRCNN_ERR_INVALID;   // 32-bit buffer offsets
+    const int mode = act == 4 ? 3 : act;
+    const WinoSkPlan p = plan_wino_sk(Cin, Cout, H, W);
+    if (p.classic) return launch_wino<2, 1, 8, 2>(x, u, bias, y, Cin, Cout, H, W, mode, 1, nullptr, 0, stream);
+    if (p.shared && (!workspace || workspace_bytes < p.ws_bytes)) return FRCNN_ERR_INVALID;
+    int *counters = p.shared ? (int *)workspace : nullptr;
+    float *slots = p.shared ? (float *)((char *)workspace + p.counters_bytes) : nullptr;
+    if (p.shared && !p.self_cleaning) FRCNN_HIP_TRY(hipMemsetAsync(counters, 0, p.counters_bytes, stream));
+    if (Cin % 8 == 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_sk_f32_kernel<true>), dim3(p.G), dim3(256), 0, stream, x, u, bias, y, Cin, Cout, H, W, mode, p.t.xtiles,
+                           p.t.ytiles, p.t.nchunks, p.total, p.pieces, p.t.piece_chunks, slots, counters);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_sk_f32_kernel<false>), dim3(p.G), dim3(256), 0, stream, x, u, bias, y, Cin, Cout, H, W, mode, p.t.xtiles,
+                           p.t.ytiles, p.t.nchunks, p.total, p.pieces, p.t.piece_chunks, slots, counters);
+    return frcnn_launch_status();
 }
 
 }  // extern "C"

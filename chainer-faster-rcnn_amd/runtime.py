@@ -526,13 +526,22 @@ class Runtime(object):
         return u
 
     def conv3x3_wino(self, x, u, bias, act=1, out=None):
-        """act 0 = + b, 1 = + b + ReLU, 4 = + b + ReLU + 2x2/2 ceil-mode max-pool."""
+        """act 0 = + b, 1 = + b + ReLU, 4 = + b + ReLU + 2x2/2 ceil-mode max-pool.  FRCNN_CONV_WINO_SK=0: the classic entry (K pieces
+        through slabs and wino_combine_kernel), for A/B measurements."""
         m, L = self.mem, self.lib
         ci, H, W = [int(v) for v in x.shape[-3:]]
         co = int(u.shape[1])
         assert int(u.shape[0]) == ci * 16
         oh, ow = ((H + 1) // 2, (W + 1) // 2) if act == 4 else (H, W)
         y = out if out is not None else m.empty((1, co, oh, ow), "f32")
+        classic = _tuning.get("FRCNN_CONV_WINO_SK", "1") == "0" or any(_tuning.get(k) is not None for k in ("FRCNN_CONV_WINO_CFG", "FRCNN_CONV_WINO_SPLIT"))
+        if not classic:            # K splits finished inside the kernel; the classic entry's own knobs (above) select the classic entry
+            ws = self.workspace("conv_wino_sk", L.frcnn_conv_wino_sk_workspace_bytes(ci, co, H, W),
+                                init=lambda w: _lib.check(L.frcnn_conv_wino_sk_workspace_init(m.ptr(w), w.shape[0], m.stream()),
+                                                          "frcnn_conv_wino_sk_workspace_init"))
+            _lib.check(L.frcnn_conv3x3_wino_sk_f32(m.ptr(x), m.ptr(u), m.ptr(bias), m.ptr(y), ci, co, H, W, int(act), m.ptr(ws), ws.shape[0],
+                                                   m.stream()), "frcnn_conv3x3_wino_sk_f32")
+            return y
         ws = self.workspace("conv_wino", L.frcnn_conv_wino_workspace_bytes(ci, co, H, W))
         _lib.check(L.frcnn_conv3x3_wino_f32(m.ptr(x), m.ptr(u), m.ptr(bias), m.ptr(y), ci, co, H, W, int(act), m.ptr(ws), ws.shape[0],
                                             m.stream()), "frcnn_conv3x3_wino_f32")

@@ -207,6 +207,26 @@ int frcnn_wino_pack_w(const float *w, int Cout, int Cin, int packed, float *u, v
 size_t frcnn_conv_wino_workspace_bytes(int Cin, int Cout, int H, int W);
 int frcnn_conv3x3_wino_f32(const float *x, const float *u, const float *bias, float *y, int Cin, int Cout, int H, int W, int act,
                            void *workspace, size_t workspace_bytes, void *stream);
+/* The same convolution finishing its K split inside the kernel (no slabs, no second launch):
+ *   frcnn_conv3x3_wino_sk_f32: the arguments and results (bit for bit) of frcnn_conv3x3_wino_f32.  On the shapes the entry above splits
+ *                           over K, every piece stores its raw Y in a 32 KB workspace slot and the piece that arrives last adds the
+ *                           pieces in piece order and writes the tile -- repeats are bit-identical, nothing ever waits.  Every other
+ *                           shape takes the classic whole-tile launch and needs no workspace.  FRCNN_CONV_WINO_SK_BALANCE=1 cuts
+ *                           those shapes into one contiguous range of (tile, 8-channel chunk) units per workgroup instead, 2 x CU
+ *                           count of them (faster; another grouping of the K sum, so the last bits differ),
+ *                           FRCNN_CONV_WINO_SK_G=n forces n such ranges on any shape (clipped to [1, tiles x chunks]),
+ *                           FRCNN_CONV_WINO_SK_PIECES=n the partition (and the bits) of the entry above under
+ *                           FRCNN_CONV_WINO_SPLIT=n; -1 = per shape, the piece count the entry above picks by itself.
+ *   workspace contract:     frcnn_conv_wino_sk_workspace_bytes (a multiple of 256, evaluated under the knobs in force) = a 64 KB page
+ *                           of tile counters followed by 2 slots per workgroup.  Zero the counter page ONCE after allocating
+ *                           (frcnn_conv_wino_sk_workspace_init); every launch leaves it zero again (the last arriver of a shared
+ *                           tile resets its counter), so no launch pays a memset.  The slots need no initialisation.  Do not hand
+ *                           the same scratch to other entry points, and do not share it between streams.  A launch that shares a
+ *                           tile refuses (FRCNN_ERR_INVALID, nothing launched) a NULL or too small workspace. */
+size_t frcnn_conv_wino_sk_workspace_bytes(int Cin, int Cout, int H, int W);
+int frcnn_conv_wino_sk_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_conv3x3_wino_sk_f32(const float *x, const float *u, const float *bias, float *y, int Cin, int Cout, int H, int W, int act,
+                              void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- RPN 1x1 heads + the reference's 18-way softmax ------------------------------------------------
  * Replaces rpn_cls_score / F.softmax / rpn_bbox_pred (models/region_proposal_network.py:118-120).

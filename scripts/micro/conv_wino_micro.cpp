@@ -2,7 +2,10 @@
 // VGG-16 layer shapes at 600 x 1000, without torch.  Per layer and arm: a captured graph of 5 back-to-back launches (outputs rotating over 3
 // buffers), bursts of graph launches between two events; the two arms alternate, `CONV_MICRO_REPS` rounds (default 3), median per arm.
 // Also the largest |wino - direct| / max|direct| per layer (a sanity check; tests/ hold the accuracy bars).
-// Usage: conv_wino_micro [layer ...]
+// --sk: the gate of the in-kernel K split (profiles/wino_sk_gate.txt) instead: the classic entry (kernel + wino_combine_kernel) against
+// frcnn_conv3x3_wino_sk_f32 with G = CU count, G = 2 x CU count and the classic partition (FRCNN_CONV_WINO_SK_PIECES), all arms interleaved;
+// per arm the median and the spread (min .. max) of the repeats.
+// Usage: conv_wino_micro [--sk] [layer ...]
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -21,9 +24,93 @@ static const Layer kLayers[] = {
     {"conv3_2", 256, 256, 150, 250, 0, 1}, {"conv3_3", 256, 256, 150, 250, 1, 1}, {"conv4_1", 256, 512, 75, 125, 0, 1}, {"conv4_2", 512, 512, 75, 125, 0, 1},
     {"conv4_3", 512, 512, 75, 125, 1, 1}, {"conv5_1", 512, 512, 38, 63, 0, 4}};
 
+static int sk_gate(const std::vector<std::string> &want) {
+    hipStream_t s; CK(hipStreamCreate(&s));
+    const int burst = getenv("CONV_MICRO_BURST") ? atoi(getenv("CONV_MICRO_BURST")) : 8;
+    const int reps = getenv("CONV_MICRO_REPS") ? atoi(getenv("CONV_MICRO_REPS")) : 3;
+    int cus = 0; CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+    std::mt19937 g(1); std::uniform_real_distribution<float> u(-1.f, 1.f);
+    constexpr int NA = 4;
+    printf("# us per launch, median [min .. max] of %d interleaved bursts of %d x 5 launches; %d CUs\n", reps * 3, burst, cus);
+    printf("# %-8s %-22s %-26s %-26s %-26s %-26s\n", "layer", "shape", "classic (kernel+combine)", "sk G=CUs", "sk G=2xCUs", "sk classic partition");
+    for (const Layer &L : kLayers) {
+        if (!want.empty() && std::find(want.begin(), want.end(), std::string(L.name)) == want.end()) continue;
+        const int OH = L.pool ? (L.h + 1) / 2 : L.h, OW = L.pool ? (L.w + 1) / 2 : L.w;
+        const size_t nx = (size_t)L.ci * L.h * L.w, nw = (size_t)9 * L.co * L.ci, ny = (size_t)L.co * OH * OW;
+        std::vector<float> hx(nx), hw(nw), hb(L.co);
+        for (auto &e : hx) e = u(g);
+        for (auto &e : hw) e = 0.05f * u(g);
+        for (auto &e : hb) e = 0.1f * u(g);
+        float *dx, *dw, *du, *db, *dy[3]; void *ws[NA]; size_t wsb[NA];
+        CK(hipMalloc(&dx, nx * 4)); CK(hipMalloc(&dw, nw * 4)); CK(hipMalloc(&du, nw / 9 * 16 * 4)); CK(hipMalloc(&db, L.co * 4));
+        for (auto &p : dy) CK(hipMalloc(&p, ny * 4));
+        CK(hipMemcpy(dx, hx.data(), nx * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dw, hw.data(), nw * 4, hipMemcpyHostToDevice));
+        CK(hipMemcpy(db, hb.data(), L.co * 4, hipMemcpyHostToDevice));
+        if (frcnn_wino_pack_w(dw, L.co, L.ci, 0, du, s) != 0) { printf("pack failed\n"); return 1; }
+        const size_t classic_ws = frcnn_conv_wino_workspace_bytes(L.ci, L.co, L.h, L.w);
+        const int pieces = classic_ws > 256 ? (int)(classic_ws / ((size_t)L.co * L.h * L.w * 4)) : 1;      // exactly the slabs
+        char v1[16], v2[16], v3[16];
+        snprintf(v1, sizeof v1, "%d", cus); snprintf(v2, sizeof v2, "%d", 2 * cus); snprintf(v3, sizeof v3, "%d", pieces);
+        const char *key[NA] = {nullptr, "FRCNN_CONV_WINO_SK_G", "FRCNN_CONV_WINO_SK_G", "FRCNN_CONV_WINO_SK_PIECES"};
+        const char *val[NA] = {nullptr, v1, v2, v3};
+        hipGraphExec_t ge[NA];
+        std::vector<float> y0(ny), y1(ny);
+        double md[NA] = {0, 0, 0, 0};
+        for (int arm = 0; arm < NA; ++arm) {
+            if (key[arm] && frcnn_set_tuning(key[arm], val[arm]) != 0) { printf("set_tuning failed\n"); return 1; }
+            wsb[arm] = arm == 0 ? classic_ws : frcnn_conv_wino_sk_workspace_bytes(L.ci, L.co, L.h, L.w);
+            CK(hipMalloc(&ws[arm], wsb[arm]));
+            if (arm > 0 && frcnn_conv_wino_sk_workspace_init(ws[arm], wsb[arm], s) != 0) { printf("workspace init failed\n"); return 1; }
+            CK(hipStreamSynchronize(s));
+            hipGraph_t gr;
+            CK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
+            bool ok = true;
+            for (int i = 0; i < 5; ++i)
+                ok = ok && (arm == 0 ? frcnn_conv3x3_wino_f32(dx, du, db, dy[i % 3], L.ci, L.co, L.h, L.w, L.pool ? 4 : 1, ws[arm], wsb[arm], s)
+                                     : frcnn_conv3x3_wino_sk_f32(dx, du, db, dy[i % 3], L.ci, L.co, L.h, L.w, L.pool ? 4 : 1, ws[arm], wsb[arm], s)) == 0;
+            CK(hipStreamEndCapture(s, &gr));
+            if (key[arm]) frcnn_set_tuning(key[arm], nullptr);
+            if (!ok) { printf("%s: launch refused (arm %d)\n", L.name, arm); return 1; }
+            CK(hipGraphInstantiate(&ge[arm], gr, nullptr, nullptr, 0));
+            CK(hipGraphDestroy(gr));
+            for (int i = 0; i < 2; ++i) CK(hipGraphLaunch(ge[arm], s));
+            CK(hipStreamSynchronize(s));
+            CK(hipMemcpy(arm == 0 ? y0.data() : y1.data(), dy[1], ny * 4, hipMemcpyDeviceToHost));
+            if (arm > 0) for (size_t i = 0; i < ny; ++i) md[arm] = std::max(md[arm], (double)fabsf(y0[i] - y1[i]));
+        }
+        hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+        std::vector<float> us[NA];
+        for (int r = -1; r < reps * 3; ++r)                  // round -1 is untimed: the first burst after the host-side setup runs at ramping clocks
+            for (int arm = 0; arm < NA; ++arm) {
+                CK(hipEventRecord(e0, s));
+                for (int b = 0; b < burst; ++b) CK(hipGraphLaunch(ge[arm], s));
+                CK(hipEventRecord(e1, s)); CK(hipEventSynchronize(e1));
+                float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
+                if (r >= 0) us[arm].push_back(ms * 200.f / burst);
+            }
+        printf("%-8s %3d->%3d %4dx%-4d p%d ", L.name, L.ci, L.co, L.h, L.w, pieces);
+        for (int arm = 0; arm < NA; ++arm) {
+            std::sort(us[arm].begin(), us[arm].end());
+            printf(" %7.1f [%6.1f ..%6.1f]", us[arm][us[arm].size() / 2], us[arm].front(), us[arm].back());
+        }
+        printf("  max|sk-classic| %.1e %.1e %.1e\n", md[1], md[2], md[3]);
+        fflush(stdout);
+        for (auto &x : ge) CK(hipGraphExecDestroy(x));
+        CK(hipFree(dx)); CK(hipFree(dw)); CK(hipFree(du)); CK(hipFree(db));
+        for (auto &p : ws) CK(hipFree(p));
+        for (auto &p : dy) CK(hipFree(p));
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     std::vector<std::string> want;
-    for (int i = 1; i < argc; ++i) want.push_back(argv[i]);
+    bool sk = false;
+    for (int i = 1; i < argc; ++i) {
+        if (std::string(argv[i]) == "--sk") sk = true;
+        else want.push_back(argv[i]);
+    }
+    if (sk) return sk_gate(want);
     hipStream_t s; CK(hipStreamCreate(&s));
     const int burst = getenv("CONV_MICRO_BURST") ? atoi(getenv("CONV_MICRO_BURST")) : 8;
     const int reps = getenv("CONV_MICRO_REPS") ? atoi(getenv("CONV_MICRO_REPS")) : 3;
