@@ -21,6 +21,7 @@
 #include <frcnn_sync.h>   // angle brackets: the test emulator shadows these headers via its include path
 #include <frcnn_buffer.h>
 #include <frcnn_intrin.h>
+#include <frcnn_wino_loop.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -49,10 +50,14 @@ struct WinoGeom {
     static_assert(SMEM * 4 <= 160 * 1024, "LDS");
 };
 
-// The main loop of one output tile (BCO couts at co0, 4 TB rows at y0, 32 columns at x0) over the K chunks [c_begin, c_end): staging ring,
-// input transform, MFMAs.  acc is zeroed here; the loop's last barrier leaves the staging buffers free for the epilogue.
-template <int CB, int TB, int CK, bool SOFF>
-__device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restrict__ x, const float *__restrict__ u, int Cin, int Cout, int H, int W,
+#ifdef FRCNN_TUNING_FORMS
+// The loop as first built (research builds only: FRCNN_CONV_WINO_LOOP=0) -- the bit reference of the shipped loop and the A/B arm of
+// profiles/wino_loop_gate.txt.  One loop body with a run-time buffer index: 16 address VALU per 8-channel chunk, step 0 of every chunk waits
+// for its own LDS reads, four instructions per DMA piece.
+// ABL (timing ablations, WRONG results, only in -DFRCNN_TIMING_ABLATIONS builds: FRCNN_CONV_WINO_ABL): 1 MFMAs only, 2 + the fragment reads and
+// the transform, 3 + the DMA issue (no per-chunk wait and barrier); 0 is the whole loop.
+template <int CB, int TB, int CK, bool SOFF, int ABL>
+__device__ __forceinline__ void wino_tile_loop_v0(float *smem, const float *__restrict__ x, const float *__restrict__ u, int Cin, int Cout, int H, int W,
                                                int x0, int y0, int co0, int c_begin, int c_end, f32x16 (&acc)[TB][4][CB]) {
     using Geo = WinoGeom<CB, TB, CK>;
     constexpr int NT = Geo::NT, BCO = Geo::BCO, HR = Geo::HR, WIT = Geo::WIT, HG = Geo::HG, HIT4 = Geo::HIT4, HVP = Geo::HVP, WBUF = Geo::WBUF;
@@ -130,13 +135,40 @@ __device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restr
     const int tr = l31 >> 4, tc = l31 & 15;              // tile of this lane: tile row (within a 4-row band), tile column
 
     issue(c_begin, 0);
+    if constexpr (ABL != 0) issue(c_begin, 1);     // both buffers hold real data: the ablated loops never wait for a later chunk
     frcnn_wait_vmcnt<0>();
     frcnn_barrier_nofence();
     if (edge_fix) edge_zero(0);
     int cur = 0;
+    [[maybe_unused]] float4 a_fix[CB];
+    [[maybe_unused]] float v_fix[TB][4];
+    if constexpr (ABL == 1) {                      // MFMAs only: operands read once, outside the loop
+        const float4 *a_base = reinterpret_cast<const float4 *>(w_lds(0)) + (khalf * 4 + wave) * BCO + l31;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) a_fix[c] = a_base[32 * c];
+#pragma unroll
+        for (int t = 0; t < TB; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v_fix[t][j] = in_lds(0)[(khalf * HR + 2 * tr + 4 * t) * kWinoPitch + kWinoLead + 2 * tc + j];
+    }
     for (int chunk = c_begin; chunk < c_end; ++chunk) {
         const bool more = chunk + 1 < c_end;
-        if (more) issue(chunk + 1, cur ^ 1);
+        if constexpr (ABL == 1) {
+#pragma unroll
+            for (int s = 0; s < CK / 2; ++s)
+#pragma unroll
+                for (int t = 0; t < TB; ++t)
+#pragma unroll
+                    for (int c = 0; c < CB; ++c) {
+                        acc[t][0][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_fix[c].x, v_fix[t][0], acc[t][0][c], 0, 0, 0);
+                        acc[t][1][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_fix[c].y, v_fix[t][1], acc[t][1][c], 0, 0, 0);
+                        acc[t][2][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_fix[c].z, v_fix[t][2], acc[t][2][c], 0, 0, 0);
+                        acc[t][3][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a_fix[c].w, v_fix[t][3], acc[t][3][c], 0, 0, 0);
+                    }
+            cur ^= 1;
+            continue;
+        }
+        if (more && (ABL == 0 || ABL == 3)) issue(chunk + 1, cur ^ 1);
         constexpr int NSTEP = CK / 2;
         const float *b_base = in_lds(cur) + (khalf * HR + 2 * tr) * kWinoPitch + kWinoLead + 2 * tc;
         const float *ba = b_base + ra * kWinoPitch, *bb = b_base + rb * kWinoPitch;
@@ -161,10 +193,14 @@ __device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restr
             __builtin_amdgcn_sched_barrier(0);       // keep the prefetch ahead of this step's MFMAs
 #pragma unroll
             for (int t = 0; t < TB; ++t) {
-                float tt[4];
+                float tt[4], v[4];
+                if constexpr (ABL == 0) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) tt[j] = fmaf(sb, db[s & 1][t][j], da[s & 1][t][j]);
-                const float v[4] = {tt[0] - tt[2], tt[1] + tt[2], tt[2] - tt[1], tt[1] - tt[3]};
+                    for (int j = 0; j < 4; ++j) tt[j] = fmaf(sb, db[s & 1][t][j], da[s & 1][t][j]);
+                    v[0] = tt[0] - tt[2]; v[1] = tt[1] + tt[2]; v[2] = tt[2] - tt[1]; v[3] = tt[1] - tt[3];
+                } else {            // the same eight VALU as a block: without the chunk's barrier the compiler packs and shuffles the C++ form (70 VALU per chunk, not 48)
+                    frcnn_wino_bt_row(sb, da[s & 1][t], db[s & 1][t], v);
+                }
 #pragma unroll
                 for (int c = 0; c < CB; ++c) {
                     const float4 av = a[s & 1][c];
@@ -175,12 +211,243 @@ __device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restr
                 }
             }
         }
-        frcnn_wait_vmcnt<0>();           // chunk + 1 has landed (nothing else is in flight)
-        frcnn_barrier_nofence();         // ... for everybody, and everybody is done reading buffer `cur`
-        if (edge_fix && more) edge_zero(cur ^ 1);
+        if constexpr (ABL == 0) {
+            frcnn_wait_vmcnt<0>();           // chunk + 1 has landed (nothing else is in flight)
+            frcnn_barrier_nofence();         // ... for everybody, and everybody is done reading buffer `cur`
+            if (edge_fix && more) edge_zero(cur ^ 1);
+        } else {
+            asm volatile("" ::: "memory");   // no instruction: the compiler keeps the chunk's shape (no LDS read carried into the next iteration)
+        }
         cur ^= 1;
     }
+    if constexpr (ABL != 0) {                // the epilogue reuses the staging buffers
+        frcnn_wait_vmcnt<0>();
+        frcnn_barrier_nofence();
+    }
+}
+#endif  // FRCNN_TUNING_FORMS
 
+
+// ---- loop forms.  kWinoLoop is the one every shipped kernel takes; research builds (-DFRCNN_TUNING_FORMS) carry the others under
+// FRCNN_CONV_WINO_LOOP as the bit reference and the A/B arms of profiles/wino_loop_gate.txt.  0: wino_tile_loop_v0.  Bit 0: the chunk loop
+// unrolled by two, so the buffer index -- every LDS base, every M0 value -- is a compile-time constant in each half, the row bases of every
+// (buffer, step) stay in registers and no address VALU is left between the MFMAs; the transform is frcnn_wino_bt_row's eight scalar VALU.
+// Bit 2: lean DMA issue (a wave's U pieces are contiguous: four per M0 write and wait state).  Bit 1: the chunk's wait and barrier stand in
+// front of the LAST step's MFMAs, the next chunk's step-0 fragments are read under them, and the right-border zeros are written before that
+// barrier by the lanes whose own pieces brought the floats along (no second barrier).  The gate's arms are 1, 5 and 7.  All forms run the
+// same operations on the same values in the same order: the results are the same bits.
+constexpr int kWinoLoop = 7;
+template <int V> struct WinoInt { static constexpr int value = V; };
+
+// The main loop of one output tile (BCO couts at co0, 4 TB rows at y0, 32 columns at x0) over the K chunks [c_begin, c_end): staging ring,
+// input transform, MFMAs.  acc is zeroed here; the loop's last barrier leaves the staging buffers free for the epilogue.  The ring starts in
+// buffer 0 at c_begin whatever c_begin is; the odd last chunk of a range runs after the loop.
+template <int CB, int TB, int CK, bool SOFF, int LF>
+__device__ __forceinline__ void wino_tile_loop(float *smem, const float *__restrict__ x, const float *__restrict__ u, int Cin, int Cout, int H, int W,
+                                               int x0, int y0, int co0, int c_begin, int c_end, f32x16 (&acc)[TB][4][CB]) {
+    using Geo = WinoGeom<CB, TB, CK>;
+    constexpr int NT = Geo::NT, BCO = Geo::BCO, HR = Geo::HR, WIT = Geo::WIT, HG = Geo::HG, HIT4 = Geo::HIT4, HVP = Geo::HVP, WBUF = Geo::WBUF;
+    constexpr int NSTEP = CK / 2;
+    constexpr bool PREFETCH = (LF & 2) != 0, LEAN = (LF & 4) != 0;
+    static_assert((LF & 1) != 0 && LF <= 7, "loop form");
+    static_assert(!PREFETCH || NSTEP % 2 == 0, "the prefetched step 0 lands in fragment slot 0 while slot 1 is in use");
+    static_assert(!LEAN || WIT % 4 == 0, "U pieces go in groups of four");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, khalf = lane >> 5;
+    const int HW = H * W;
+    const int K4 = Cin * 4;
+
+    const frcnn_buf_t xbuf = frcnn_make_buf(x, (uint32_t)((size_t)Cin * HW * sizeof(float)));
+    const frcnn_buf_t ubuf = frcnn_make_buf(u, (uint32_t)((size_t)K4 * Cout * 4 * sizeof(float)));
+    const uint32_t u_chunk_bytes = (uint32_t)(CK * 4 * Cout * 4) * 4u, x_chunk_bytes = (uint32_t)(CK * HW) * 4u;
+
+    uint32_t woff[WIT], hoff[HIT4];
+#pragma unroll
+    for (int q = 0; q < WIT; ++q) {                          // LEAN: wave w stages float4s [w * WIT * 64, (w + 1) * WIT * 64) of the slab, piece q & 3 of a group
+        const int v = LEAN ? (wave * WIT + q) * 64 + lane : tid + q * NT;      // through the immediate offset 1024 (q & 3): 16 v >= 1024 q keeps it non-negative
+        const int row = v / BCO, c4 = v % BCO;
+        woff[q] = (uint32_t)(row * Cout * 4 + (co0 + c4) * 4) * 4u - (LEAN ? (uint32_t)(q & 3) * 1024u : 0u);
+    }
+#pragma unroll
+    for (int q = 0; q < HIT4; ++q) {                         // group e4 = (channel, halo row, group of four columns)
+        const int e4 = tid + q * NT;
+        const int c = e4 / (HR * 10), rem = e4 % (HR * 10);
+        const int hr = rem / 10, g4 = rem % 10;
+        const int gy = y0 - 1 + hr, gx = x0 - 4 + 4 * g4;
+        const bool inside = e4 < HG && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        hoff[q] = inside ? (uint32_t)(c * HW + gy * W + gx) * 4u : kBufOob;
+    }
+    auto in_lds = [&](int buf) { return smem + 2 * WBUF + buf * HVP; };
+    // a 16-byte group that straddles the right image border (W % 4 != 0) brings up to three floats of the next row along: zero them
+    const int fix_lo = W - x0 + 4, fix_hi = (fix_lo + 3) & ~3;
+    const bool edge_fix = (W & 3) != 0 && fix_lo > 0 && fix_lo < kWinoPitch;
+    auto edge_zero = [&](int buf) {
+        const int row = tid / 3, i = fix_lo + tid % 3;
+        if (row < CK * HR && i < fix_hi) in_lds(buf)[row * kWinoPitch + i] = 0.0f;
+        frcnn_barrier_nofence();
+    };
+    // the same zeros before the chunk's barrier instead of behind a second one: the lane whose own piece brought the straddling group along
+    // overwrites them once its pieces have landed (after its vmcnt(0) wait), and the barrier that publishes the chunk publishes them too
+    int zfix[HIT4];                                      // float index of this lane's straddling group in a halo buffer, or -1
+#pragma unroll
+    for (int q = 0; q < HIT4; ++q) {
+        const int e4 = tid + q * NT;
+        zfix[q] = (edge_fix && e4 < HG && e4 % 10 == (fix_lo >> 2)) ? e4 * 4 : -1;
+    }
+    auto edge_zero_own = [&](int buf) {
+        const int k0 = fix_lo & 3;                       // 1 .. 3: floats k0 .. 3 of the group lie past the border
+#pragma unroll
+        for (int q = 0; q < HIT4; ++q)
+            if (zfix[q] >= 0) {
+                float *g = in_lds(buf) + zfix[q];
+                if (k0 <= 1) g[1] = 0.0f;
+                if (k0 <= 2) g[2] = 0.0f;
+                g[3] = 0.0f;
+            }
+    };
+    auto issue = [&](int chunk, auto bufc) {
+        constexpr int buf = decltype(bufc)::value;
+        float *wl = smem + buf * WBUF, *il = smem + 2 * WBUF + buf * HVP;
+        auto pieces = [&](frcnn_buf_t ub, frcnn_buf_t xb_, uint32_t wb, uint32_t xb) {
+            if constexpr (LEAN) {
+#pragma unroll
+                for (int q = 0; q < WIT; q += 4)
+                    frcnn_buf_load_lds_b128_x4(ub, wl + (wave * WIT + q) * 64 * 4, woff[q], woff[q + 1], woff[q + 2], woff[q + 3], wb);
+            } else {
+#pragma unroll
+                for (int q = 0; q < WIT; ++q) frcnn_buf_load_lds_b128(ub, wl + (q * NT + wave * 64) * 4, woff[q], wb);
+            }
+#pragma unroll
+            for (int q = 0; q < HIT4; ++q)
+                if ((q + 1) * NT * 4 <= HVP || (wave * 64 + q * NT) * 4 < HVP)
+                    frcnn_buf_load_lds_b128(xb_, il + (q * NT + wave * 64) * 4, hoff[q], xb);
+        };
+        if constexpr (SOFF) {               // Cin is a whole number of chunks: the chunk offset rides in the scalar offset
+            pieces(ubuf, xbuf, (uint32_t)chunk * u_chunk_bytes, (uint32_t)chunk * x_chunk_bytes);
+        } else {                            // ragged last chunk: per-chunk descriptors whose range ends at the tensor's end
+            const long long wrem = (long long)(K4 - chunk * CK * 4) * Cout * 4, xrem = (long long)(Cin - chunk * CK) * HW;
+            pieces(frcnn_make_buf(u + (size_t)chunk * CK * 4 * Cout * 4, (uint32_t)((wrem > 0 ? wrem : 0) * sizeof(float))),
+                   frcnn_make_buf(x + (size_t)chunk * CK * HW, (uint32_t)((xrem > 0 ? xrem : 0) * sizeof(float))), 0, 0);
+        }
+    };
+
+#pragma unroll
+    for (int t = 0; t < TB; ++t)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < CB; ++c)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][k][c][r] = 0.0f;
+
+    // row w of B^T d = d[ra] + sb * d[rb]:  w0 d0 - d2,  w1 d1 + d2,  w2 d2 - d1,  w3 d1 - d3  (fmaf with sb = +-1 is the exact add / subtract)
+    const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
+    const int rb = wave == 0 ? 2 : (wave == 1 ? 2 : (wave == 2 ? 1 : 3));
+    const float sb = wave == 1 ? 1.0f : -1.0f;
+    const int tr = l31 >> 4, tc = l31 & 15;              // tile of this lane: tile row (within a 4-row band), tile column
+    const int d_off = (khalf * HR + 2 * tr) * kWinoPitch + kWinoLead + 2 * tc, a_off = (khalf * 4 + wave) * BCO + l31;
+
+    // the row bases of every (buffer, step), pinned in registers: a step's ds_read2_b32 pairs reach 255 dwords, the next channel pair lies 480 away
+    const float *bap[2][NSTEP], *bbp[2][NSTEP];
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int s = 0; s < NSTEP; ++s) {
+            bap[b][s] = frcnn_pin_lds(smem + 2 * WBUF + b * HVP + d_off + ra * kWinoPitch + 2 * s * HR * kWinoPitch);
+            bbp[b][s] = frcnn_pin_lds(smem + 2 * WBUF + b * HVP + d_off + rb * kWinoPitch + 2 * s * HR * kWinoPitch);
+        }
+    float4 a[2][CB];
+    float da[2][TB][4], db[2][TB][4];
+    auto frag = [&](auto bufc, int s, int slot) {        // step s of the chunk in buffer `buf` -> fragment slot
+        constexpr int buf = decltype(bufc)::value;
+        const float *ba = bap[buf][s], *bb = bbp[buf][s];
+        const float4 *a_base = reinterpret_cast<const float4 *>(smem + buf * WBUF) + a_off;
+#pragma unroll
+        for (int c = 0; c < CB; ++c) a[slot][c] = a_base[2 * s * 4 * BCO + 32 * c];
+#pragma unroll
+        for (int t = 0; t < TB; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                da[slot][t][j] = ba[4 * t * kWinoPitch + j];
+                db[slot][t][j] = bb[4 * t * kWinoPitch + j];
+            }
+    };
+    auto step = [&](int slot) {                          // the transform of one channel pair and its 4 CB TB MFMAs
+#pragma unroll
+        for (int t = 0; t < TB; ++t) {
+            float v[4];                                   // tt = fmaf(sb, db, da);  v = {tt0 - tt2, tt1 + tt2, tt2 - tt1, tt1 - tt3}
+            frcnn_wino_bt_row(sb, da[slot][t], db[slot][t], v);
+#pragma unroll
+            for (int c = 0; c < CB; ++c) {
+                const float4 av = a[slot][c];
+                acc[t][0][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, v[0], acc[t][0][c], 0, 0, 0);
+                acc[t][1][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, v[1], acc[t][1][c], 0, 0, 0);
+                acc[t][2][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, v[2], acc[t][2][c], 0, 0, 0);
+                acc[t][3][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, v[3], acc[t][3][c], 0, 0, 0);
+            }
+        }
+    };
+    // one chunk, in buffer `buf`; LAST: known at compile time to be the range's last chunk (more is false)
+    auto half = [&](auto bufc, auto lastc, int chunk, const bool more) {
+        constexpr int buf = decltype(bufc)::value;
+        constexpr bool LAST = decltype(lastc)::value != 0;
+        if (more) issue(chunk + 1, WinoInt<buf ^ 1>{});
+        if constexpr (!PREFETCH) frag(bufc, 0, 0);
+#pragma unroll
+        for (int s = 0; s < NSTEP; ++s) {
+            if (s + 1 < NSTEP) {
+                frag(bufc, s + 1, (s + 1) & 1);
+            } else if constexpr (PREFETCH) {
+                frcnn_wait_vmcnt<0>();           // chunk + 1 has landed (nothing else is in flight)
+                if (edge_fix && more) edge_zero_own(buf ^ 1);
+                frcnn_barrier_nofence();         // ... for everybody, and everybody has read the last of buffer `buf` (the barrier drains the LDS reads)
+                // the next chunk's step 0, under this chunk's last MFMAs (unconditional: behind a range's last chunk it reads stale floats nobody uses)
+                if constexpr (!LAST) frag(WinoInt<buf ^ 1>{}, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);       // keep the prefetch ahead of this step's MFMAs
+            step(s & 1);
+        }
+        if constexpr (!PREFETCH) {
+            frcnn_wait_vmcnt<0>();
+            frcnn_barrier_nofence();
+            if (edge_fix && more) edge_zero(buf ^ 1);
+        }
+    };
+
+    issue(c_begin, WinoInt<0>{});
+    frcnn_wait_vmcnt<0>();
+    if constexpr (PREFETCH) {
+        if (edge_fix) edge_zero_own(0);
+        frcnn_barrier_nofence();
+    } else {
+        frcnn_barrier_nofence();
+        if (edge_fix) edge_zero(0);
+    }
+    if (c_begin >= c_end) return;
+    if constexpr (PREFETCH) frag(WinoInt<0>{}, 0, 0);
+    int chunk = c_begin;
+    for (; chunk + 1 < c_end; chunk += 2) {              // one way out of the loop: the accumulators stay where they are
+        half(WinoInt<0>{}, WinoInt<0>{}, chunk, true);
+        half(WinoInt<1>{}, WinoInt<0>{}, chunk + 1, chunk + 2 < c_end);
+    }
+    if (chunk < c_end) half(WinoInt<0>{}, WinoInt<1>{}, chunk, false);  // the odd last chunk
+}
+
+// the loop form LF (0: wino_tile_loop_v0 with its timing ablation ABL, research builds only)
+template <int CB, int TB, int CK, bool SOFF, int LF, int ABL>
+__device__ __forceinline__ void wino_loop(float *smem, const float *__restrict__ x, const float *__restrict__ u, int Cin, int Cout, int H, int W, int x0,
+                                          int y0, int co0, int c_begin, int c_end, f32x16 (&acc)[TB][4][CB]) {
+    if constexpr (LF == 0) {
+#ifdef FRCNN_TUNING_FORMS
+        wino_tile_loop_v0<CB, TB, CK, SOFF, ABL>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+#else
+        static_assert(LF != 0, "the first loop is a research form");
+#endif
+    } else {
+        static_assert(ABL == 0, "the ablations are cut into the first loop");
+        wino_tile_loop<CB, TB, CK, SOFF, LF>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+    }
 }
 
 // ---- epilogue, first half.  Z[w][0] = M[w][0] + M[w][1] + M[w][2],  Z[w][1] = M[w][1] - M[w][2] - M[w][3]  (M A, this wave's row), exchanged
@@ -257,13 +524,12 @@ __device__ __forceinline__ void wino_emit(float *__restrict__ y, const float (&y
 }
 
 // mode bit 0: ReLU, bit 1: fused 2x2/2 max-pool (ceil mode; ReLU implied), bit 2: K piece -> raw Y (no bias) into y + piece * Cout*H*W
-template <int CB, int TB, int CK, int BPC, bool SOFF>
-__global__ void __launch_bounds__(256, BPC)
-conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
-                     int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, int piece_chunks) {
+template <int CB, int TB, int CK, bool SOFF, int LF, int ABL>
+__device__ __forceinline__ void wino_classic_body(float *smem, const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias,
+                                                  float *__restrict__ y, int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks,
+                                                  int piece_chunks) {
     using Geo = WinoGeom<CB, TB, CK>;
     constexpr int BCO = Geo::BCO;
-    __shared__ __attribute__((aligned(16))) float smem[Geo::SMEM];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -284,7 +550,7 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
     const int c_end = nchunks < c_begin + piece_chunks ? nchunks : c_begin + piece_chunks;
 
     f32x16 acc[TB][4][CB];
-    wino_tile_loop<CB, TB, CK, SOFF>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+    wino_loop<CB, TB, CK, SOFF, LF, ABL>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
     wino_z_exchange<CB, TB>(smem, acc);
     const bool relu = (mode & 1) != 0, pool = (mode & 2) != 0, partial = (mode & 4) != 0;
     const int tr = l31 >> 4, tc = l31 & 15;
@@ -308,6 +574,24 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
     }
 }
 
+template <int CB, int TB, int CK, int BPC, bool SOFF>
+__global__ void __launch_bounds__(256, BPC)
+conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                     int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, int piece_chunks) {
+    __shared__ __attribute__((aligned(16))) float smem[WinoGeom<CB, TB, CK>::SMEM];
+    wino_classic_body<CB, TB, CK, SOFF, kWinoLoop, 0>(smem, x, u, bias, y, Cin, Cout, H, W, mode, xtiles, ytiles, nchunks, piece_chunks);
+}
+#ifdef FRCNN_TUNING_FORMS
+// the same kernel around another loop form / timing ablation (research builds: FRCNN_CONV_WINO_LOOP, FRCNN_CONV_WINO_ABL)
+template <int CB, int TB, int CK, int BPC, bool SOFF, int LF, int ABL>
+__global__ void __launch_bounds__(256, BPC)
+wino_lab_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                    int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, int piece_chunks) {
+    __shared__ __attribute__((aligned(16))) float smem[WinoGeom<CB, TB, CK>::SMEM];
+    wino_classic_body<CB, TB, CK, SOFF, LF, ABL>(smem, x, u, bias, y, Cin, Cout, H, W, mode, xtiles, ytiles, nchunks, piece_chunks);
+}
+#endif
+
 // ---- the form that finishes its K split itself (frcnn_conv3x3_wino_sk_f32).  Work distribution as conv.hip's stream-K: the unit is one
 // 8-channel chunk of one output tile, total = ntiles * nchunks units, workgroup g of G takes the contiguous range [g*total/G, (g+1)*total/G)
 // -- or, with pieces > 0 (FRCNN_CONV_WINO_SK_PIECES), the classic launch's partition: tile g / pieces, its chunks
@@ -318,17 +602,15 @@ conv_wino_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, c
 // barriers and takes a ticket on the tile's counter; the holder of ticket P-1 acquires, puts the counter back to zero and adds the P
 // pieces in ascending piece order (s = y_0; s += y_k, wino_combine_kernel's order), then bias / ReLU / pool through the same code as the
 // main epilogue.  Nobody waits for anybody: correctness does not depend on residency or arrival order.
-template <bool SOFF>
-__global__ void __launch_bounds__(256, 2)
-wino_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
-                   int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, long long total, int pieces, int piece_chunks,
-                   float *__restrict__ slots, int *__restrict__ tile_counters) {
+template <bool SOFF, int LF, int ABL>
+__device__ __forceinline__ void wino_sk_body(float *smem, const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias,
+                                             float *__restrict__ y, int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks,
+                                             long long total, int pieces, int piece_chunks, float *__restrict__ slots, int *__restrict__ tile_counters) {
     constexpr int CB = 2, TB = 1, CK = 8;
     using Geo = WinoGeom<CB, TB, CK>;
     constexpr int BCO = Geo::BCO, NT = Geo::NT;
     constexpr int SLOT_V = TB * CB * 4;                      // float4s per thread and slot
     constexpr size_t kSlotFloats = (size_t)NT * SLOT_V * 4;
-    __shared__ __attribute__((aligned(16))) float smem[Geo::SMEM];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -368,7 +650,7 @@ wino_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, con
         if (it != it_begin) __syncthreads();                 // the previous tile's epilogue is done with the LDS the ring restarts in
 
         f32x16 acc[TB][4][CB];
-        wino_tile_loop<CB, TB, CK, SOFF>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
+        wino_loop<CB, TB, CK, SOFF, LF, ABL>(smem, x, u, Cin, Cout, H, W, x0, y0, co0, c_begin, c_end, acc);
         wino_z_exchange<CB, TB>(smem, acc);
 
         const bool whole = c_begin == 0 && c_end == nchunks;
@@ -448,6 +730,25 @@ wino_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, con
     }
 }
 
+template <bool SOFF>
+__global__ void __launch_bounds__(256, 2)
+wino_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                   int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, long long total, int pieces, int piece_chunks,
+                   float *__restrict__ slots, int *__restrict__ tile_counters) {
+    __shared__ __attribute__((aligned(16))) float smem[WinoGeom<2, 1, 8>::SMEM];
+    wino_sk_body<SOFF, kWinoLoop, 0>(smem, x, u, bias, y, Cin, Cout, H, W, mode, xtiles, ytiles, nchunks, total, pieces, piece_chunks, slots, tile_counters);
+}
+#ifdef FRCNN_TUNING_FORMS
+template <bool SOFF, int LF, int ABL>
+__global__ void __launch_bounds__(256, 2)
+wino_lab_sk_f32_kernel(const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias, float *__restrict__ y,
+                       int Cin, int Cout, int H, int W, int mode, int xtiles, int ytiles, int nchunks, long long total, int pieces, int piece_chunks,
+                       float *__restrict__ slots, int *__restrict__ tile_counters) {
+    __shared__ __attribute__((aligned(16))) float smem[WinoGeom<2, 1, 8>::SMEM];
+    wino_sk_body<SOFF, LF, ABL>(smem, x, u, bias, y, Cin, Cout, H, W, mode, xtiles, ytiles, nchunks, total, pieces, piece_chunks, slots, tile_counters);
+}
+#endif
+
 // the K pieces of a split launch: slabs added in piece order, then bias, ReLU and (mode bit 1) the 2x2/2 ceil-mode max-pool
 __global__ void __launch_bounds__(256)
 wino_combine_kernel(const float *__restrict__ ws, const float *__restrict__ bias, float *__restrict__ y, int P, int C, int H, int W, int mode) {
@@ -514,6 +815,28 @@ static WinoPlan plan_wino(int Cin, int Cout, int H, int W, int pieces) {
     return p;
 }
 
+// FRCNN_CONV_WINO_LOOP: the loop form of every launch (-1: not in this build).  The product library carries kWinoLoop alone and refuses every
+// other value; research builds (-DFRCNN_TUNING_FORMS) also carry 0 (the first loop: every shape) and the gate's arms 1, 5, 7 (whole 8-channel chunks)
+static int wino_loop_form() {
+    const char *v = frcnn_tune("FRCNN_CONV_WINO_LOOP");
+    if (!v) return kWinoLoop;
+    const int f = atoi(v);
+#ifdef FRCNN_TUNING_FORMS
+    return (f == 0 || f == 1 || f == 5 || f == 7) ? f : -1;
+#else
+    return f == kWinoLoop ? f : -1;
+#endif
+}
+// FRCNN_CONV_WINO_ABL: a timing ablation of the first loop (WRONG results; -DFRCNN_TUNING_FORMS -DFRCNN_TIMING_ABLATIONS builds with FRCNN_CONV_WINO_LOOP=0)
+static int wino_loop_ablation() {
+    const int a = frcnn_tune_int("FRCNN_CONV_WINO_ABL", 0);
+#if defined(FRCNN_TUNING_FORMS) && defined(FRCNN_TIMING_ABLATIONS)
+    return (a >= 0 && a <= 3) ? a : -1;
+#else
+    return a == 0 ? 0 : -1;
+#endif
+}
+
 template <int CB, int TB, int CK, int BPC>
 static int launch_wino(const float *x, const float *u, const float *bias, float *y, int Cin, int Cout, int H, int W, int mode, int pieces,
                        void *workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -524,12 +847,34 @@ static int launch_wino(const float *x, const float *u, const float *bias, float 
     const int kmode = split ? 4 : mode;
     float *out = split ? (float *)workspace : y;
     const int G = p.ntiles * p.pieces;
-    if (Cin % CK == 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wino_f32_kernel<CB, TB, CK, BPC, true>), dim3(G), dim3(256), 0, stream, x, u, bias, out, Cin, Cout, H, W,
-                           kmode, p.xtiles, p.ytiles, p.nchunks, p.piece_chunks);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_wino_f32_kernel<CB, TB, CK, BPC, false>), dim3(G), dim3(256), 0, stream, x, u, bias, out, Cin, Cout, H, W,
-                           kmode, p.xtiles, p.ytiles, p.nchunks, p.piece_chunks);
+    const int lf = wino_loop_form(), abl = wino_loop_ablation();
+    if (lf < 0 || abl < 0) return FRCNN_ERR_INVALID;
+    const bool soff = Cin % CK == 0;
+#define FRCNN_WINO_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), dim3(G), dim3(256), 0, stream, x, u, bias, out, Cin, Cout, H, W, kmode, \
+                                                  p.xtiles, p.ytiles, p.nchunks, p.piece_chunks)
+    if (lf == kWinoLoop && abl == 0) {
+        if (soff) FRCNN_WINO_LAUNCH(conv_wino_f32_kernel<CB, TB, CK, BPC, true>);
+        else FRCNN_WINO_LAUNCH(conv_wino_f32_kernel<CB, TB, CK, BPC, false>);
+    }
+#ifdef FRCNN_TUNING_FORMS
+    else if (lf == 0 && abl == 0) {
+        if (soff) FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, CK, BPC, true, 0, 0>);
+        else FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, CK, BPC, false, 0, 0>);
+    } else if (CK == 8 && soff && abl == 0) {          // the gate's arms: whole 8-channel chunks only
+        if (lf == 1) FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 1, 0>);
+        else if (lf == 5) FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 5, 0>);
+        else FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 7, 0>);
+    }
+#ifdef FRCNN_TIMING_ABLATIONS
+    else if (CK == 8 && soff && lf == 0) {
+        if (abl == 1) FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 0, 1>);
+        else if (abl == 2) FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 0, 2>);
+        else FRCNN_WINO_LAUNCH(wino_lab_f32_kernel<CB, TB, 8, BPC, true, 0, 3>);
+    }
+#endif
+#endif
+    else return FRCNN_ERR_INVALID;                      // a form this build does not carry: refused, never substituted
+#undef FRCNN_WINO_LAUNCH
     if (split) {
         const size_t total = (size_t)Cout * ((mode & 2) ? (size_t)((H + 1) / 2) * ((W + 1) / 2) : (size_t)H * W);
         const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
@@ -668,17 +1013,39 @@ int frcnn_conv3x3_wino_sk_f32(const float *x, const float *u, const float *bias,
     if ((size_t)Cin * H * W * 4 >= (1ull << 31) || (size_t)Cin * 16 * Cout * 4 >= (1ull << 31)) return FRCNN_ERR_INVALID;   // 32-bit buffer offsets
     const int mode = act == 4 ? 3 : act;
     const WinoSkPlan p = plan_wino_sk(Cin, Cout, H, W);
+    const int lf = wino_loop_form(), abl = wino_loop_ablation();
+    if (lf < 0 || abl < 0) return FRCNN_ERR_INVALID;
     if (p.classic) return launch_wino<2, 1, 8, 2>(x, u, bias, y, Cin, Cout, H, W, mode, 1, nullptr, 0, stream);
     if (p.shared && (!workspace || workspace_bytes < p.ws_bytes)) return FRCNN_ERR_INVALID;
     int *counters = p.shared ? (int *)workspace : nullptr;
     float *slots = p.shared ? (float *)((char *)workspace + p.counters_bytes) : nullptr;
     if (p.shared && !p.self_cleaning) FRCNN_HIP_TRY(hipMemsetAsync(counters, 0, p.counters_bytes, stream));
-    if (Cin % 8 == 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_sk_f32_kernel<true>), dim3(p.G), dim3(256), 0, stream, x, u, bias, y, Cin, Cout, H, W, mode, p.t.xtiles,
-                           p.t.ytiles, p.t.nchunks, p.total, p.pieces, p.t.piece_chunks, slots, counters);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(wino_sk_f32_kernel<false>), dim3(p.G), dim3(256), 0, stream, x, u, bias, y, Cin, Cout, H, W, mode, p.t.xtiles,
-                           p.t.ytiles, p.t.nchunks, p.total, p.pieces, p.t.piece_chunks, slots, counters);
+    const bool soff = Cin % 8 == 0;
+#define FRCNN_WINO_LAUNCH(...) hipLaunchKernelGGL(HIP_KERNEL_NAME(__VA_ARGS__), dim3(p.G), dim3(256), 0, stream, x, u, bias, y, Cin, Cout, H, W, mode, p.t.xtiles, \
+                                                  p.t.ytiles, p.t.nchunks, p.total, p.pieces, p.t.piece_chunks, slots, counters)
+    if (lf == kWinoLoop && abl == 0) {
+        if (soff) FRCNN_WINO_LAUNCH(wino_sk_f32_kernel<true>);
+        else FRCNN_WINO_LAUNCH(wino_sk_f32_kernel<false>);
+    }
+#ifdef FRCNN_TUNING_FORMS
+    else if (lf == 0 && abl == 0) {
+        if (soff) FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 0, 0>);
+        else FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<false, 0, 0>);
+    } else if (soff && abl == 0) {
+        if (lf == 1) FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 1, 0>);
+        else if (lf == 5) FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 5, 0>);
+        else FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 7, 0>);
+    }
+#ifdef FRCNN_TIMING_ABLATIONS
+    else if (soff && lf == 0) {
+        if (abl == 1) FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 0, 1>);
+        else if (abl == 2) FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 0, 2>);
+        else FRCNN_WINO_LAUNCH(wino_lab_sk_f32_kernel<true, 0, 3>);
+    }
+#endif
+#endif
+    else return FRCNN_ERR_INVALID;
+#undef FRCNN_WINO_LAUNCH
     return frcnn_launch_status();
 }
 

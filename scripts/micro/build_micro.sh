@@ -43,3 +43,10 @@ if [ "${MICRO_CONV_F32_FORMS:-0}" = "1" ]; then
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip scripts/micro/conv_f32_micro.cpp -I include -L scripts/micro/_bin -lconv_forms -Wl,-rpath,'$ORIGIN' -o scripts/micro/_bin/conv_f32_micro_forms
   echo built-conv-forms
 fi
+# research build of the Winograd convolution alone (-DFRCNN_TUNING_FORMS: the loop forms of FRCNN_CONV_WINO_LOOP; -DFRCNN_TIMING_ABLATIONS: FRCNN_CONV_WINO_ABL,
+# WRONG results by design) + the same harness against it (--loop, --abl, --sk): opt-in
+if [ "${MICRO_WINO_LAB:-0}" = "1" ]; then
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -w -DFRCNN_TUNING_FORMS -DFRCNN_TIMING_ABLATIONS -I include -I chainer-faster-rcnn_amd/csrc -shared chainer-faster-rcnn_amd/csrc/conv_wino.hip chainer-faster-rcnn_amd/csrc/abi.hip -o scripts/micro/_bin/libwino_lab.so
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -x hip -DWINO_MICRO_LAB_ONLY scripts/micro/conv_wino_micro.cpp -I include -L scripts/micro/_bin -lwino_lab -Wl,-rpath,'$ORIGIN' -o scripts/micro/_bin/conv_wino_micro_lab
+  echo built-wino-lab
+fi
