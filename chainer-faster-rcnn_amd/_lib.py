@@ -168,6 +168,11 @@ SIGNATURES = {
     "frcnn_im2col7x7s2_f16": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "frcnn_maxpool3x3s2_f16": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_subsample2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
+    "frcnn_bn_workspace_bytes": (_S, [_I, _I]),
+    "frcnn_bn_train_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _S, _P]),
+    "frcnn_bn_train_bwd_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _S, _P]),
+    "frcnn_maxpool3x3s2_bwd_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "frcnn_subsample2_bwd_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_bbox_overlaps_f64": (_I, [_P, _I, _P, _I, _P, _P]),
     "frcnn_anchor_target_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "frcnn_anchor_target": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _S, _P]),

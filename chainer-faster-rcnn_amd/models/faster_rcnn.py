@@ -152,6 +152,8 @@ class FasterRCNN(object):
         layout first)."""
         self._head_dirty = True
         self._derived_dirty = True
+        if hasattr(self.trunk, "mark_params_updated"):       # the ResNet trunk: its folded inference weights and input-gradient packings
+            self.trunk.mark_params_updated()
         for link in list(getattr(self.trunk, "links", {}).values()) + [getattr(self.RPN, "rpn_conv_3x3", None)]:
             if getattr(link, "Wu", None) is not None:
                 link.wu_stale = True                         # the Winograd weights: rebuilt from the packed ones at their next use

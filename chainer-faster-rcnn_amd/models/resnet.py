@@ -10,7 +10,13 @@ as an explicit im2col + 1x1, a stride-2 1x1 as subsample + 1x1; BN is folded int
 (W' = W * gamma/sqrt(var+eps), b' = beta - mean * gamma/sqrt(var+eps), eps = 2e-5: chainer's default); the bottleneck
 tail relu(conv3 + shortcut) is fused into conv3's epilogue.  Parameters keep chainer's link paths
 (`conv1/W`, `bn1/gamma|beta|avg_mean|avg_var`, `res3/a/conv1/W`, `res3/b1/bn2/gamma`, ...).
-Train-mode BatchNormalization (batch statistics) is not implemented: the trunk is inference-only.
+
+Training (fp32): with `train = True` (the reference's default, models/resnet.py:41-45: `test = not self.train`) every BatchNormalization
+runs on the statistics of the map it is given (csrc/bn_train.hip): each convolution runs unfolded with act = 0, frcnn_bn_train_fwd_f32
+normalises its output with the ReLU -- and in a bottleneck tail the shortcut sum -- fused, and updates the running statistics.  The call
+keeps a tape (conv inputs, pre-BN maps z, outputs y, saved mean and 1/std); `backward(g, grads)` walks it in reverse and fills the gradient
+of every W (packed layout), gamma, beta and `conv1/b`.  `mark_params_updated()` re-folds the inference weights from the current parameters
+and running statistics.  The 16-bit trunks are inference-only.
 
 conv_dtype="bf16" runs the trunk on the 16-bit chain (channel-blocked [C/16][H][W][16] maps, operands rounded to nearest even, fp32
 accumulation): the stem as frcnn_im2col7x7s2_bf16 + the 1x1 kernel (Kp = 160), frcnn_maxpool3x3s2_bf16, every 1x1 (stride 2 folded into
@@ -25,16 +31,22 @@ from ..runtime import default_runtime
 BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 STAGES = [("res2", 64, 64, 256, 1), ("res3", 256, 128, 512, 2), ("res4", 512, 256, 1024, 2), ("res5", 1024, 512, 2048, 2)]
 BN_EPS = 2e-5
+BN_DECAY = 0.9          # L.BatchNormalization's default: running = decay * running + (1 - decay) * batch statistic
 
 
 def block_names(n):
     return ["a"] + ["b%d" % i for i in range(1, n)]
 
 
-def conv_specs(blocks):
+def stages(base_width=64):
+    """STAGES with every width scaled by base_width / 64 (64: the published network)"""
+    return [(s, ci * base_width // 64, mid * base_width // 64, co * base_width // 64, st) for s, ci, mid, co, st in STAGES]
+
+
+def conv_specs(blocks, base_width=64):
     """[(link path of the conv, link path of its BN, cin, cout, ksize)] in execution order."""
-    out = [("conv1", "bn1", 3, 64, 7)]
-    for (stage, cin, mid, cout, _), n in zip(STAGES, blocks):
+    out = [("conv1", "bn1", 3, base_width, 7)]
+    for (stage, cin, mid, cout, _), n in zip(stages(base_width), blocks):
         for b in block_names(n):
             i = cin if b == "a" else cout
             p = "%s/%s/" % (stage, b)
@@ -42,6 +54,22 @@ def conv_specs(blocks):
             if b == "a":
                 out.append((p + "conv4", p + "bn4", i, cout, 1))
     return out
+
+
+def pack_w(W, ksize):
+    """(co,ci,k,k) -> the convolution kernels' (ci*k*k [the 7x7 stem's im2col rows padded to a multiple of 8], co) fp32"""
+    W = np.asarray(W, dtype=np.float32)
+    co = W.shape[0]
+    packed = np.ascontiguousarray(W.reshape(co, -1).T)
+    if ksize == 7:
+        kp = (packed.shape[0] + 7) // 8 * 8
+        packed = np.concatenate([packed, np.zeros((kp - packed.shape[0], co), np.float32)], 0)
+    return packed
+
+
+def unpack_w(packed, co, ci, ksize):
+    """pack_w's inverse (the stem's padding rows dropped)"""
+    return np.ascontiguousarray(np.asarray(packed)[:ci * ksize * ksize].T).reshape(co, ci, ksize, ksize)
 
 
 class _FoldedConv(object):
@@ -73,7 +101,7 @@ class _FoldedConv(object):
 
 
 class ResNet(object):
-    def __init__(self, n_layers=101, runtime=None, blocks=None, conv_dtype="f32"):
+    def __init__(self, n_layers=101, runtime=None, blocks=None, conv_dtype="f32", base_width=64):
         if conv_dtype == "f32s":
             raise ValueError("ResNet: conv_dtype 'f32s' (split-product fp32) is not implemented for the ResNet trunk; use 'f32' or 'bf16'")
         if conv_dtype not in ("f32", "bf16"):
@@ -81,35 +109,200 @@ class ResNet(object):
         self.rt = runtime or default_runtime()
         self.blocks = tuple(blocks) if blocks is not None else BLOCKS[n_layers]
         self.conv_dtype = conv_dtype
+        if int(base_width) < 64 or int(base_width) % 64:
+            raise ValueError("ResNet: base_width must be a multiple of 64 (the fp32 convolution kernels take Cout %% 64 == 0, and every width is "
+                             "some layer's Cout, forward or in its input-gradient convolution), not %r" % (base_width,))
+        self.base_width = int(base_width)
+        self.stages = stages(self.base_width)
         self.train = False
         self.convs = {}
+        self.tp = {}                                           # train-mode parameters on the device, by link path below the prefix
+        self.tape = None
+        self._wd, self._wd_stale = {}, True                    # input-gradient packings of tp's weights, re-packed after an update
+        self._zero_bias = {}
+        self._fold_stale = False
         self.skip_nchw = False
         self.feat_bf16 = self.feat_shape = None
 
     def load_params(self, params, prefix="trunk/"):
-        for conv, bn, ci, co, k in conv_specs(self.blocks):
+        m = self.rt.mem
+        for conv, bn, ci, co, k in conv_specs(self.blocks, self.base_width):
             W = params[prefix + conv + "/W"]
             assert tuple(W.shape) == (co, ci, k, k), (conv, tuple(W.shape))
             stats = [params[prefix + bn + "/" + n] for n in ("gamma", "beta", "avg_mean", "avg_var")]
             self.convs[conv] = _FoldedConv(self.rt, W, stats, k, conv_bias=params.get(prefix + conv + "/b"), half=self.conv_dtype == "bf16")
+            if self.conv_dtype == "f32":                       # the unfolded parameters, for the train-mode pass
+                self.tp[conv + "/W"] = m.from_numpy(pack_w(W, k))
+                for n, v in zip(("gamma", "beta", "avg_mean", "avg_var"), stats):
+                    self.tp[bn + "/" + n] = m.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
+                if (prefix + conv + "/b") in params:
+                    self.tp[conv + "/b"] = m.from_numpy(np.ascontiguousarray(params[prefix + conv + "/b"], dtype=np.float32))
+        self._wd, self._wd_stale = {}, True
+        self._fold_stale = False
+
+    # ---- the trainable form ---------------------------------------------------------------------------------------------------------------
+    def param_specs(self):
+        """[(key below the prefix, Chainer-layout shape, kind)] of everything an optimizer moves, in execution order; kind 'W' (stored packed,
+        see pack_w / unpack_w), 'v' (a vector stored as it is)."""
+        out = []
+        for conv, bn, ci, co, k in conv_specs(self.blocks, self.base_width):
+            out.append((conv + "/W", (co, ci, k, k), "W"))
+            if (conv + "/b") in self.tp:
+                out.append((conv + "/b", (co,), "v"))
+            out += [(bn + "/gamma", (co,), "v"), (bn + "/beta", (co,), "v")]
+        return out
+
+    def persistent_keys(self):
+        """the running statistics: saved with a snapshot, moved by the forward pass, not by the optimizer"""
+        return [bn + "/" + n for _, bn, _, _, _ in conv_specs(self.blocks, self.base_width) for n in ("avg_mean", "avg_var")]
+
+    def mark_params_updated(self):
+        """the parameters (or running statistics) changed on the device: the input-gradient packings are rebuilt at the next backward pass and the
+        folded inference weights at the next test-mode call"""
+        self._wd_stale = True
+        self._fold_stale = True
+
+    def params_host(self, prefix="trunk/"):
+        """the current parameters and running statistics in Chainer's layout, keyed like load_params' input"""
+        m = self.rt.mem
+        out = {}
+        for conv, bn, ci, co, k in conv_specs(self.blocks, self.base_width):
+            out[prefix + conv + "/W"] = unpack_w(m.to_numpy(self.tp[conv + "/W"]), co, ci, k)
+            if (conv + "/b") in self.tp:
+                out[prefix + conv + "/b"] = m.to_numpy(self.tp[conv + "/b"])
+            for n in ("gamma", "beta", "avg_mean", "avg_var"):
+                out[prefix + bn + "/" + n] = m.to_numpy(self.tp[bn + "/" + n])
+        return out
+
+    def _refold(self):
+        p = self.params_host("")
+        for conv, bn, ci, co, k in conv_specs(self.blocks, self.base_width):
+            self.convs[conv] = _FoldedConv(self.rt, p[conv + "/W"], [p[bn + "/" + n] for n in ("gamma", "beta", "avg_mean", "avg_var")], k,
+                                           conv_bias=p.get(conv + "/b"), half=False)
+        self._fold_stale = False
+
+    def _zeros(self, n):
+        if n not in self._zero_bias:
+            self._zero_bias[n] = self.rt.mem.zeros((n,), "f32")
+        return self._zero_bias[n]
+
+    def _conv_bn(self, conv, bn, x, ksize, relu, residual=None):
+        """one convolution (unfolded, act 0) + BatchNormalization on the map's own statistics [+ residual] [+ ReLU]; taped"""
+        rt, tp = self.rt, self.tp
+        W = tp[conv + "/W"]
+        co = int(W.shape[1])
+        z = rt.conv_ex(x, W, tp.get(conv + "/b", self._zeros(co)), ksize, act=0)
+        y, mean, rstd = rt.bn_train_fwd(z, tp[bn + "/gamma"], tp[bn + "/beta"], residual=residual, relu=relu, eps=BN_EPS, decay=BN_DECAY,
+                                        running_mean=tp[bn + "/avg_mean"], running_var=tp[bn + "/avg_var"])
+        self.tape[conv] = dict(x=x, z=z, y=y, mean=mean, rstd=rstd, relu=relu, bn=bn, ksize=ksize)
+        return y
+
+    def _call_train(self, h, timer=None, collect=None):
+        rt = self.rt
+        if not self.tp:
+            raise ValueError("ResNet: load_params first")
+        self.tape = {}
+        h = self._conv_bn("conv1", "bn1", rt.im2col7x7s2(h, int(self.tp["conv1/W"].shape[0])), 1, True)
+        h = rt.maxpool3x3s2(h)
+        for (stage, _, _, _, stride), n in zip(self.stages, self.blocks):
+            for b in block_names(n):
+                p = "%s/%s/" % (stage, b)
+                xin = rt.subsample2(h) if (b == "a" and stride == 2) else h
+                self.tape[p] = dict(hw=(int(h.shape[2]), int(h.shape[3])), strided=xin is not h)
+                shortcut = self._conv_bn(p + "conv4", p + "bn4", xin, 1, False) if b == "a" else h
+                t = self._conv_bn(p + "conv1", p + "bn1", xin, 1, True)
+                t = self._conv_bn(p + "conv2", p + "bn2", t, 3, True)
+                h = self._conv_bn(p + "conv3", p + "bn3", t, 1, True, residual=shortcut)
+            if timer:
+                timer.mark(stage)
+        if collect is not None:                                # the tape's maps by link path: (pre-BN z, output y)
+            for name, t in self.tape.items():
+                if "z" in t:
+                    collect[name] = (t["z"], t["y"])
+        self._fold_stale = True                                # the running statistics moved
+        return h
+
+    def _dgrad_w(self, conv, ksize):
+        """the input-gradient packing of a layer's current weights; after an update ALL layers are re-packed at the first request, sixteen per
+        launch (frcnn_pack_conv_dgrad_w_many), into buffers that are kept"""
+        if self._wd_stale:
+            rt, todo = self.rt, []
+            for c, _, ci, co, k in conv_specs(self.blocks, self.base_width)[1:]:          # (the stem needs no input gradient)
+                if c not in self._wd:
+                    self._wd[c] = rt.mem.empty((co * k * k, ci), "f32")
+                todo.append((self.tp[c + "/W"], self._wd[c], k))
+            for i in range(0, len(todo), 16):
+                rt.pack_conv_dgrad_w_many(todo[i:i + 16])
+            self._wd_stale = False
+        return self._wd[conv]
+
+    def _conv_bn_bwd(self, conv, dy, grads, want_dres=False, want_dx=True, ready=None):
+        """backward of _conv_bn: fills grads[conv/W], grads[bn/gamma], grads[bn/beta] -> (dL/dx or None, dres or None)"""
+        rt, t = self.rt, self.tape[conv]
+        bn, ks = t["bn"], t["ksize"]
+        dz, dg, db, dres = rt.bn_train_bwd(dy, t["y"] if t["relu"] else None, t["z"], self.tp[bn + "/gamma"], t["mean"], t["rstd"], want_dres=want_dres,
+                                           dgamma=grads.get(bn + "/gamma"), dbeta=grads.get(bn + "/beta"))
+        grads[bn + "/gamma"], grads[bn + "/beta"] = dg, db
+        grads[conv + "/W"] = rt.conv_wgrad(t["x"], dz, ks, out=grads.get(conv + "/W"))
+        if (conv + "/b") in self.tp:
+            grads[conv + "/b"] = rt.bias_grad(dz, out=grads.get(conv + "/b"))
+        if ready is not None:
+            ready(conv)                                        # a data-parallel trainer: this layer's gradients are enqueued
+        dx = None
+        if want_dx:
+            ci = int(t["x"].shape[1])
+            dx = rt.conv_ex(dz, self._dgrad_w(conv, ks), self._zeros(ci), ks, act=0)
+        return dx, dres
+
+    def backward(self, g, grads=None, ready=None):
+        """g = dL/d res5 of the last train-mode call -> grads: {key below the prefix: device array}, the gradient of every W (in the packed
+        layout of tp), gamma, beta and conv1/b.  Arrays already present in `grads` are written in place (a trainer's arena views); `ready(conv)`
+        is called once a layer's gradients are enqueued, in reverse execution order (conv3, conv2, conv1, conv4 within a block `a`)."""
+        rt = self.rt
+        if self.tape is None:
+            raise ValueError("ResNet.backward: no train-mode forward pass to differentiate")
+        grads = {} if grads is None else grads
+        g = rt.asarray(unwrap(g), "f32")
+        for (stage, _, _, _, stride), n in reversed(list(zip(self.stages, self.blocks))):
+            for b in reversed(block_names(n)):
+                p = "%s/%s/" % (stage, b)
+                # g = dL/d(block output); its ReLU mask is applied by bn3's backward, which also hands back dres = the shortcut's gradient
+                d, dres = self._conv_bn_bwd(p + "conv3", g, grads, want_dres=True, ready=ready)
+                d, _ = self._conv_bn_bwd(p + "conv2", d, grads, ready=ready)
+                d, _ = self._conv_bn_bwd(p + "conv1", d, grads, ready=ready)
+                if b == "a":
+                    d4, _ = self._conv_bn_bwd(p + "conv4", dres, grads, ready=ready)
+                    d = rt.add(d, d4, out=d)
+                    if self.tape[p]["strided"]:
+                        d = rt.subsample2_bwd(d, *self.tape[p]["hw"])
+                else:
+                    d = rt.add(d, dres, out=d)                 # the identity shortcut
+                g = d
+        g = rt.maxpool3x3s2_bwd(self.tape["conv1"]["y"], g)
+        self._conv_bn_bwd("conv1", g, grads, want_dx=False, ready=ready)     # the image needs no gradient
+        return grads
 
     def _conv(self, name, x, act=1, residual=None):
         c = self.convs[name]
         return self.rt.conv_ex(x, c.Wp, c.b, 1 if c.ksize == 7 else c.ksize, act=act, mask=residual)
 
     def __call__(self, x, timer=None, collect=None):
-        if self.train:
-            raise NotImplementedError("train-mode BatchNormalization (batch statistics) is not part of this path")
         rt = self.rt
         h = rt.asarray(unwrap(x), "f32")
         assert h.ndim == 4 and int(h.shape[0]) == 1, "batch size 1 (models/faster_rcnn.py:77)"
+        if self.train:
+            if self.conv_dtype != "f32":
+                raise ValueError("ResNet: train-mode BatchNormalization runs on the fp32 trunk only (conv_dtype='f32'); the 16-bit trunks are inference-only")
+            return self._call_train(h, timer, collect)
         if self.conv_dtype == "bf16":
             return self._call_bf16(h, timer, collect)
         if collect is not None:
-            raise ValueError("ResNet: per-layer collection is a feature of the 16-bit trunk (conv_dtype='bf16')")
+            raise ValueError("ResNet: per-layer collection is a feature of the 16-bit trunk (conv_dtype='bf16') and of the train-mode pass")
+        if self._fold_stale:
+            self._refold()
         h = self._conv("conv1", rt.im2col7x7s2(h, int(self.convs["conv1"].Wp.shape[0])))      # conv1 + bn1 + relu
         h = rt.maxpool3x3s2(h)
-        for (stage, _, _, _, stride), n in zip(STAGES, self.blocks):
+        for (stage, _, _, _, stride), n in zip(self.stages, self.blocks):
             for b in block_names(n):
                 p = "%s/%s/" % (stage, b)
                 xin = rt.subsample2(h) if (b == "a" and stride == 2) else h                # stride sits on the first 1x1 (and the shortcut)
@@ -137,11 +330,11 @@ class ResNet(object):
 
         stem = self.convs["conv1"]
         h = self._h1x1("conv1", rt.im2col7x7s2_bf16(x, stem.cin))                         # conv1 + bn1 + relu
-        keep("conv1", h, 64)
+        keep("conv1", h, self.base_width)
         h = rt.maxpool3x3s2_bf16(h)
-        keep("pool1", h, 64)
-        cout = 64
-        for (stage, _, mid, cout, stride), n in zip(STAGES, self.blocks):
+        keep("pool1", h, self.base_width)
+        cout = self.base_width
+        for (stage, _, mid, cout, stride), n in zip(self.stages, self.blocks):
             for b in block_names(n):
                 p = "%s/%s/" % (stage, b)
                 s = stride if b == "a" else 1                                             # stride sits on the first 1x1 (and the shortcut)

@@ -917,6 +917,50 @@ class Runtime(object):
         _lib.check(L.frcnn_subsample2_f32(m.ptr(x), m.ptr(y), C, H, W, m.stream()), "frcnn_subsample2_f32")
         return y
 
+    # the trainable trunk (csrc/bn_train.hip): BatchNormalization on batch statistics and the adjoints of the two glue kernels above
+    def bn_train_fwd(self, z, gamma, beta, residual=None, relu=False, eps=2e-5, decay=0.9, running_mean=None, running_var=None, out=None):
+        """z (1,C,H,W) -> (y, save_mean (C,), save_rstd (C,)): y = [relu](gamma * (z - mean) * rstd + beta [+ residual]) on the map's own
+        statistics; running_mean / running_var (C,) are updated in place when given."""
+        m, L = self.mem, self.lib
+        C, H, W = [int(v) for v in z.shape[-3:]]
+        y = out if out is not None else m.empty((1, C, H, W), "f32")
+        mean, rstd = m.empty((C,), "f32"), m.empty((C,), "f32")
+        ws = self.workspace("bn_train", L.frcnn_bn_workspace_bytes(C, H * W))
+        _lib.check(L.frcnn_bn_train_fwd_f32(m.ptr(z), m.ptr(gamma), m.ptr(beta), m.ptr(residual), int(bool(relu)), C, H * W, float(eps), float(decay),
+                                            m.ptr(y), m.ptr(mean), m.ptr(rstd), m.ptr(running_mean), m.ptr(running_var), m.ptr(ws), ws.shape[0],
+                                            m.stream()), "frcnn_bn_train_fwd_f32")
+        return y, mean, rstd
+
+    def bn_train_bwd(self, dy, y, z, gamma, save_mean, save_rstd, want_dres=False, dgamma=None, dbeta=None):
+        """-> (dz, dgamma, dbeta, dres or None).  y = the forward output when the layer ended in a ReLU (its mask is y > 0), else None;
+        dres = dy under that mask, the gradient of the fused residual input."""
+        m, L = self.mem, self.lib
+        C, H, W = [int(v) for v in z.shape[-3:]]
+        dz = m.empty((1, C, H, W), "f32")
+        dres = m.empty((1, C, H, W), "f32") if want_dres else None
+        dgamma = dgamma if dgamma is not None else m.empty((C,), "f32")
+        dbeta = dbeta if dbeta is not None else m.empty((C,), "f32")
+        ws = self.workspace("bn_train", L.frcnn_bn_workspace_bytes(C, H * W))
+        _lib.check(L.frcnn_bn_train_bwd_f32(m.ptr(dy), m.ptr(y), m.ptr(z), m.ptr(gamma), m.ptr(save_mean), m.ptr(save_rstd), C, H * W, m.ptr(dz),
+                                            m.ptr(dgamma), m.ptr(dbeta), m.ptr(dres), m.ptr(ws), ws.shape[0], m.stream()), "frcnn_bn_train_bwd_f32")
+        return dz, dgamma, dbeta, dres
+
+    def maxpool3x3s2_bwd(self, x, dy):
+        m, L = self.mem, self.lib
+        C, H, W = [int(v) for v in x.shape[-3:]]
+        dx = m.empty((1, C, H, W), "f32")
+        _lib.check(L.frcnn_maxpool3x3s2_bwd_f32(m.ptr(x), m.ptr(dy), m.ptr(dx), C, H, W, m.stream()), "frcnn_maxpool3x3s2_bwd_f32")
+        return dx
+
+    def subsample2_bwd(self, dy, H, W):
+        """dy (1,C,ceil(H/2),ceil(W/2)) -> dx (1,C,H,W): dy at the even positions, 0 elsewhere."""
+        m, L = self.mem, self.lib
+        C = int(dy.shape[-3])
+        assert (int(dy.shape[-2]), int(dy.shape[-1])) == ((int(H) - 1) // 2 + 1, (int(W) - 1) // 2 + 1)
+        dx = m.empty((1, C, int(H), int(W)), "f32")
+        _lib.check(L.frcnn_subsample2_bwd_f32(m.ptr(dy), m.ptr(dx), C, int(H), int(W), m.stream()), "frcnn_subsample2_bwd_f32")
+        return dx
+
     # the same pieces on the 16-bit chain (csrc/resnet_bf16.hip; through self.hlib, so with_half("f16") runs the fp16 twins)
     def conv1x1_bf16(self, x, w_packed, bias, cin, cout, stride=1, act=1, residual=None):
         """x [CinP/16][H][W][16] -> [CoutP/16][Ho][Wo][16] (Ho = ceil(H/stride)): act 0 none, 1 ReLU, 3 relu(conv + b + residual)."""

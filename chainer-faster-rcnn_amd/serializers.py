@@ -14,7 +14,18 @@ import numpy as np
 def namedparams(model):
     """Yield (link path, device array in chainer's layout) for every parameter the model holds."""
     rt = model.rt
-    for name, link in model.trunk.links.items():
+    if getattr(model.trunk, "tp", None):
+        # the ResNet trunk (models/resnet.py): W unpacked from the kernels' layout; gamma, beta, conv1/b; and the running statistics, which
+        # chainer's serializer writes next to them as the BatchNormalization links' persistents (no optimizer state belongs to those two)
+        from .models.resnet import conv_specs
+        tp = model.trunk.tp
+        for conv, bn, ci, co, k in conv_specs(model.trunk.blocks, model.trunk.base_width):
+            yield "trunk/%s/W" % conv, rt.transpose(tp[conv + "/W"])[:, :ci * k * k].reshape(co, ci, k, k)
+            if (conv + "/b") in tp:
+                yield "trunk/%s/b" % conv, tp[conv + "/b"]
+            for n in ("gamma", "beta", "avg_mean", "avg_var"):
+                yield "trunk/%s/%s" % (bn, n), tp["%s/%s" % (bn, n)]
+    for name, link in getattr(model.trunk, "links", {}).items():
         yield "trunk/%s/W" % name, link.W
         yield "trunk/%s/b" % name, link.b
     rpn = model.RPN

@@ -56,13 +56,13 @@ def load_npz(path, model):
     return _load(path, model)
 
 
-def resnet_params(n_layers=101, seed=2, blocks=None, prefix="trunk/"):
+def resnet_params(n_layers=101, seed=2, blocks=None, prefix="trunk/", base_width=64):
     """Random-init ResNet trunk in chainer's ResNetLayers naming: He-normal convolutions (no bias) and BatchNormalization
     statistics drawn so that test-mode activations stay O(1) through 100 layers."""
     from .models.resnet import BLOCKS, conv_specs
     rs = np.random.RandomState(seed)
     p = {}
-    for conv, bn, ci, co, k in conv_specs(tuple(blocks) if blocks is not None else BLOCKS[n_layers]):
+    for conv, bn, ci, co, k in conv_specs(tuple(blocks) if blocks is not None else BLOCKS[n_layers], base_width):
         gain = 0.5 if conv.endswith("conv3") or conv.endswith("conv4") else 1.0      # the two summands of a block: keep the sum O(1)
         p[prefix + conv + "/W"] = (rs.randn(co, ci, k, k) * gain * np.sqrt(2.0 / (ci * k * k))).astype(np.float32)
         p[prefix + bn + "/gamma"] = rs.uniform(0.5, 1.0, co).astype(np.float32)

@@ -253,6 +253,79 @@ def trunk_backward_bf16(trainer, layer_inputs, g):
     return g
 
 
+def _is_resnet(model):
+    from .models.resnet import ResNet
+    return isinstance(getattr(model, "trunk", None), ResNet)
+
+
+class _ResNetTrunk(object):
+    """What RPNTrainer needs from a ResNet trunk (models/resnet.py), so that one trainer drives both trunk families: the arena segments of its
+    parameters, their adoption into the arena, forward-with-tape and backward, and the layout conversions of a flat buffer.  Segment keys are
+    the link paths below `trunk/` (`conv1/W`, `bn1/gamma`, `res3/a/conv4/W`, ...); a W segment holds the convolution kernels' packed layout.
+    The buffer is laid out in EXECUTION order -- a block's projection shortcut conv4 before its conv1 -- so the backward pass fills it from
+    the end and _BucketedAllReduce's tail buckets close as they do for VGG."""
+
+    def __init__(self, trunk):
+        from .models.resnet import conv_specs
+        self.trunk = trunk
+        if trunk.conv_dtype != "f32":
+            raise ValueError("RPNTrainer: ResNet training runs on the fp32 trunk (conv_dtype='f32'); mixed-precision ResNet training is not built")
+        if not trunk.tp:
+            raise ValueError("RPNTrainer: load the model's parameters first")
+        specs = conv_specs(trunk.blocks, trunk.base_width)
+        order, i = [], 0
+        while i < len(specs):                                        # (conv1, conv2, conv3, conv4) of a block `a` -> (conv4, conv1, conv2, conv3)
+            if specs[i][0].endswith("/a/conv1"):
+                order += [specs[i + 3]] + specs[i:i + 3]
+                i += 4
+            else:
+                order.append(specs[i])
+                i += 1
+        self.specs = order
+        self.names = [c[0] for c in order]
+
+    def segments(self):
+        """[(key, shape)] in buffer order"""
+        tp, out = self.trunk.tp, []
+        for conv, bn, ci, co, k in self.specs:
+            out.append((conv + "/W", tuple(int(v) for v in tp[conv + "/W"].shape)))
+            if (conv + "/b") in tp:
+                out.append((conv + "/b", (co,)))
+            out += [(bn + "/gamma", (co,)), (bn + "/beta", (co,))]
+        return out
+
+    def adopt(self, arena):
+        tp = self.trunk.tp
+        for key, _ in self.segments():
+            tp[key] = arena._adopt(key, tp[key])
+
+    def feat_hw(self, H, W):
+        f = lambda v: (v - 1) // 2 + 1                               # noqa: E731
+        H, W = (f(H) - 2) // 2 + 1, (f(W) - 2) // 2 + 1              # the stem's stride, pool1 (cover_all)
+        for _, _, _, _, stride in self.trunk.stages:
+            if stride == 2:
+                H, W = f(H), f(W)
+        return H, W
+
+    def to_chainer(self, seg, out):
+        from .models.resnet import unpack_w
+        for conv, bn, ci, co, k in self.specs:
+            out["trunk/" + conv + "/W"] = unpack_w(seg(conv + "/W"), co, ci, k)
+            if (conv + "/b") in self.trunk.tp:
+                out["trunk/" + conv + "/b"] = seg(conv + "/b").copy()
+            for n in ("gamma", "beta"):
+                out["trunk/%s/%s" % (bn, n)] = seg(bn + "/" + n).copy()
+
+    def from_chainer(self, arrays, put):
+        from .models.resnet import pack_w
+        for conv, bn, ci, co, k in self.specs:
+            if "trunk/" + conv + "/W" in arrays:
+                put(conv + "/W", pack_w(arrays["trunk/" + conv + "/W"], k))
+            for key in (conv + "/b", bn + "/gamma", bn + "/beta"):
+                if "trunk/" + key in arrays and key in self.trunk.tp:
+                    put(key, arrays["trunk/" + key])
+
+
 class _Seg(object):
     def __init__(self, name, shape, offset):
         self.name, self.shape, self.offset = name, tuple(shape), offset
@@ -489,6 +562,10 @@ class RPNTrainer(_BucketedAllReduce):
             raise ValueError("RPNTrainer: conv_math must be 'mfma', 'split', 'bf16' or 'f16', not %r" % (conv_math,))
         if loss_scale is not None and conv_math != "f16":
             raise ValueError("RPNTrainer: loss_scale belongs to conv_math='f16', not %r" % (conv_math,))
+        if _is_resnet(model) and conv_math != "mfma":
+            raise ValueError("RPNTrainer: a ResNet model trains with conv_math='mfma' (fp32) only, not %r: split-product and mixed-precision "
+                             "ResNet training are not built" % (conv_math,))
+        self.resnet = _ResNetTrunk(model.trunk) if _is_resnet(model) else None
         self.model, self.rt = model, model.rt
         self.lr, self.momentum = lr, momentum
         self._init_optimizer("RPNTrainer", opt, opt_args, weight_decay)      # (AdaGrad / RMSprop: self.lr is the rule's own)
@@ -501,7 +578,8 @@ class RPNTrainer(_BucketedAllReduce):
         self.atl = AnchorTargetLayer(rpn.proposal_layer._feat_stride, runtime=rt)
         self.atl._anchors = rpn.proposal_layer._anchors
         self.atl._num_anchors = rpn.proposal_layer._num_anchors
-        self.layers = model.trunk.layers
+        # (a ResNet trunk's parameters are not `links`: self.resnet lays them out, and rpn_conv_3x3 is the only conv link of this list)
+        self.layers = model.trunk.layers if self.resnet is None else []
         self.convs = [(l[0], model.trunk.links[l[0]]) for l in self.layers if l != "pool"] + [("rpn_conv_3x3", rpn.rpn_conv_3x3)]
         # ---- one flat buffer each for parameters, gradients, velocities; every segment 256-byte aligned
         segs, off = [], 0
@@ -512,6 +590,9 @@ class RPNTrainer(_BucketedAllReduce):
             off += (s.size + 63) // 64 * 64
             return s
         self.seg = {}
+        if self.resnet is not None:
+            for key, shape in self.resnet.segments():
+                self.seg[key] = add(key, shape)
         for name, link in self.convs:
             self.seg[name + "/W"] = add(name + "/W", link.Wp.shape)
             self.seg[name + "/b"] = add(name + "/b", link.b.shape)
@@ -525,9 +606,10 @@ class RPNTrainer(_BucketedAllReduce):
         self._ensure_adopted()
         self.grad = {k: rt.mem.view(self.G, s.offset, s.shape) for k, s in self.seg.items()}
         # weights of the input-gradient convolutions (re-packed from the current weights every step)
-        self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32") for name, link in self.convs[1:]}
+        self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32")
+                   for name, link in (self.convs[1:] if self.resnet is None else self.convs)}       # (VGG's first layer needs no input gradient)
         self.wd_heads = rt.mem.empty((int(wp.shape[1]), int(wp.shape[0])), "f32")
-        self.zero_bias = rt.mem.zeros((512,), "f32")
+        self.zero_bias = rt.mem.zeros((512 if self.resnet is None else max(512, int(rpn.rpn_conv_3x3.cin)),), "f32")
         if conv_math == "split":                                      # split weights of the forward / input-gradient convolutions (re-packed every step)
             pad = rt.bf16_pad
             big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
@@ -545,10 +627,12 @@ class RPNTrainer(_BucketedAllReduce):
             self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
         self._draw = None
         self.iteration = 0
-        self._plan_buckets([n for n, _ in self.convs])       # heads follow rpn_conv_3x3 in the buffer and precede it in time
+        self._plan_buckets((self.resnet.names if self.resnet is not None else []) + [n for n, _ in self.convs])       # heads follow rpn_conv_3x3 in the buffer and precede it in time
 
     def _ensure_adopted(self):
         rpn = self.model.RPN
+        if self.resnet is not None:
+            self.resnet.adopt(self)
         for name, link in self.convs:
             link.Wp = self._adopt(name + "/W", link.Wp)
             link.b = self._adopt(name + "/b", link.b)
@@ -574,6 +658,8 @@ class RPNTrainer(_BucketedAllReduce):
         for l in self.layers:
             if l == "pool":
                 H, W = (H + 1) // 2, (W + 1) // 2
+        if self.resnet is not None:
+            H, W = self.resnet.feat_hw(H, W)
         with rt.mem.early_stream(unwrap(gt_boxes)):                   # its own stream: it must not wait for the previous step's backward
             labels, targets, inds, n_in, _ = self.atl.forward_device(H, W, gt_boxes, im_h, im_w)      # (host ground truth; a DEVICE array is waited for)
         rt.mem.join_early_stream(labels, targets, inds)
@@ -590,6 +676,13 @@ class RPNTrainer(_BucketedAllReduce):
             feat, inputs, feat_b = trunk_forward_bf16(self, x)
             link = rpn.rpn_conv_3x3
             _, mid = rth.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_bf16=False)
+        elif self.resnet is not None:
+            # train-mode BatchNormalization trunk: the forward pass keeps its own tape; its input-gradient packings are rebuilt after an update
+            rt.pack_conv_dgrad_w_many([(rpn.rpn_conv_3x3.Wp, self.wd["rpn_conv_3x3"], 3), (rpn._heads_packed[0], self.wd_heads, 1)])
+            self._dgrad_packed = True
+            model.trunk.train = True
+            feat, inputs = model.trunk(x), []
+            mid = rpn.rpn_conv_3x3(feat, relu=True)
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): one launch
             if _tuning.get("FRCNN_DGRAD_PACK") != "each":          # (=each: A/B hook, one launch per layer inside the backward pass)
@@ -628,6 +721,19 @@ class RPNTrainer(_BucketedAllReduce):
         if not getattr(self, "_dgrad_packed", False):
             rt.pack_conv_dgrad_w(rpn._heads_packed[0], 1, out=self.wd_heads)
         g = rt.conv_ex(draw.reshape(1, NP, H, W), self.wd_heads, self.zero_bias, 1, act=2, mask=mid)
+        if self.resnet is not None:
+            # ---- rpn_conv_3x3 (g is already under its ReLU mask), then the trunk's own backward pass: res5's ReLU mask is bn3's to apply
+            with _grad_stream(rt, feat, g):
+                rt.conv_wgrad(feat, g, 3, out=self.grad["rpn_conv_3x3/W"])
+                rt.bias_grad(g, out=self.grad["rpn_conv_3x3/b"])
+                self._grads_ready("rpn_conv_3x3")
+            g = rt.conv_ex(g, self.wd["rpn_conv_3x3"], self.zero_bias, 3, act=0)
+            rt.mem.join_aux_stream("grad")
+            model.trunk.backward(g, self.grad, ready=self._grads_ready)
+            self._dgrad_packed = False
+            if self.run_proposal_layer:
+                rt.mem.join_side_stream()
+            return dict(losses=losses)
         # ---- rpn_conv_3x3, then the trunk in reverse
         backward = {"split": trunk_backward_split, "bf16": trunk_backward_bf16, "f16": trunk_backward_bf16}.get(self.conv_math, trunk_backward)
         backward(self, list(zip(self.layers, inputs)) + [(("rpn_conv_3x3", 0, 0), feat)], g)
@@ -687,6 +793,8 @@ class RPNTrainer(_BucketedAllReduce):
         def seg(key):
             sg = self.seg[key]
             return host[sg.offset:sg.offset + sg.size].reshape(sg.shape)
+        if self.resnet is not None:
+            self.resnet.to_chainer(seg, out)
         for name, link in self.convs:
             prefix = "RPN/" if name == "rpn_conv_3x3" else "trunk/"
             out[prefix + name + "/W"] = np.ascontiguousarray(seg(name + "/W").T).reshape(link.cout, link.cin, 3, 3)
@@ -704,6 +812,8 @@ class RPNTrainer(_BucketedAllReduce):
         def put(key, val):
             sg = self.seg[key]
             host[sg.offset:sg.offset + sg.size] = np.asarray(val, dtype=np.float32).reshape(-1)
+        if self.resnet is not None:
+            self.resnet.from_chainer(arrays, put)
         for name, link in self.convs:
             prefix = "RPN/" if name == "rpn_conv_3x3" else "trunk/"
             if prefix + name + "/W" in arrays:
@@ -761,6 +871,8 @@ class RCNNTrainer(_BucketedAllReduce):
         loss_scale (precision="f16" only): "dynamic" (the default), a power of two (static), or a dict of LossScaler's constants.
         opt, opt_args, weight_decay=None: the update rule and its hyper-parameters, as in RPNTrainer."""
         from .models.proposal_target_layer import ProposalTargetLayer
+        if _is_resnet(model):
+            raise ValueError("RCNNTrainer: stage-2 training of a ResNet model is not built (RPNTrainer trains its trunk and RPN)")
         if conv_math not in ("mfma", "split"):
             raise ValueError("RCNNTrainer: conv_math is the arithmetic of the trunk's fp32 convolutions, 'mfma' or 'split', not %r "
                              "(16-bit operands: precision='bf16' / 'f16')" % (conv_math,))

@@ -591,6 +591,29 @@ int frcnn_softmax_channels_f32(const float *score, int n_ch, int HW, float *prob
 int frcnn_im2col7x7s2_f32(const float *x, int Cin, int H, int W, int Kp, float *cols, void *stream);
 int frcnn_maxpool3x3s2_f32(const float *x, float *y, int C, int H, int W, void *stream);
 int frcnn_subsample2_f32(const float *x, float *y, int C, int H, int W, void *stream);
+/* ---- The trainable trunk (csrc/bn_train.hip) -- the reference's models/resnet.py:41-45: `self.train = True` runs ResNetLayers with
+ * `test = not self.train`, i.e. L.BatchNormalization on BATCH statistics, and its backward pass.  fp32, batch 1: a map is (C, HW), m = HW.
+ * frcnn_bn_train_fwd_f32: y = [relu](gamma * (z - mean) * rstd + beta [+ residual]); mean = the channel's mean over its HW values,
+ *   rstd = 1 / sqrt(var + eps) with the biased variance; save_mean (C) and save_rstd (C) are what the backward pass reads.  running_mean /
+ *   running_var (C, both optional) are updated in place: rm = decay * rm + (1 - decay) * mean,
+ *   rv = decay * rv + (1 - decay) * m / max(m - 1, 1) * (var + eps).  residual (C, HW) optional; relu 0 / 1.
+ * frcnn_bn_train_bwd_f32: with g = dy where y > 0 (y = the forward output; NULL: no ReLU, g = dy) and xhat = (z - save_mean) * save_rstd:
+ *   dbeta = sum g, dgamma = sum g * xhat, dz = gamma * rstd * (g - dbeta / m - xhat * dgamma / m); dres (optional) = g, the gradient of the
+ *   fused residual input.
+ * Both are two launches over (C, parts) workgroups: sums of a slice accumulated in double into `workspace` (frcnn_bn_workspace_bytes; 8-byte
+ * aligned, needs no initialisation), then added in part order by the launch that applies them.  No atomics: the same inputs give the same
+ * bits.  FRCNN_ERR_INVALID (nothing launched): a NULL required pointer, C or HW < 1, a NULL or too small workspace.
+ * frcnn_maxpool3x3s2_bwd_f32: adjoint of frcnn_maxpool3x3s2_f32 (x = the pool's input (C,H,W), dy (C,OH,OW), dx (C,H,W)): a window's dy goes to its
+ *   first maximum in row-major order; every element of dx is written, sums in ascending window order.
+ * frcnn_subsample2_bwd_f32: adjoint of frcnn_subsample2_f32: dx[c][2i][2j] = dy[c][i][j], every other element of dx (C,H,W) written as 0. */
+size_t frcnn_bn_workspace_bytes(int C, int HW);
+int frcnn_bn_train_fwd_f32(const float *z, const float *gamma, const float *beta, const float *residual, int relu, int C, int HW, double eps,
+                           double decay, float *y, float *save_mean, float *save_rstd, float *running_mean, float *running_var, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int frcnn_bn_train_bwd_f32(const float *dy, const float *y, const float *z, const float *gamma, const float *save_mean, const float *save_rstd, int C,
+                           int HW, float *dz, float *dgamma, float *dbeta, float *dres, void *workspace, size_t workspace_bytes, void *stream);
+int frcnn_maxpool3x3s2_bwd_f32(const float *x, const float *dy, float *dx, int C, int H, int W, void *stream);
+int frcnn_subsample2_bwd_f32(const float *dy, float *dx, int C, int H, int W, void *stream);
 /* The same trunk pieces on the 16-bit chain (csrc/resnet_bf16.hip; fp16 twins below) -- /root/reference/models/resnet.py:11-45 -> chainer ResNetLayers
  * (conv1 7x7/2 + bn1 + relu, pool1 3x3/2, the res2..res5 bottlenecks' 1x1 convolutions with BatchNormalization folded in).  Maps are channel-blocked
  * [CP/16][H][W][16] 16-bit, CP = frcnn_bf16_padded_channels(C); weights frcnn_bf16_pack_conv_w(..., ksize 1) of the folded (Cout, Cin) matrix.
