@@ -163,7 +163,7 @@ class FasterRCNN(object):
             # remember them all, most recent last, so that later syncs win where two trainers share the trunk
             # A NEW trainer of a class that is already registered supersedes the old one (a script that builds a trainer per stage or
             # epoch kept every one's W / G / V arenas alive, ~1.6 GB each for VGG-16, and re-synced them all on every snapshot): it has adopted
-            # every parameter of that set into its own arena (_ParamArena._adopt copies the links' current windows), so the old trainer's packed
+            # every parameter of that set into its own arena (train._Trainer._adopt copies the links' current windows), so the old trainer's packed
             # weights are stale copies from then on.  Not a weak reference: a trainer the caller dropped WITHOUT a successor still holds the only
             # packed weights its links point into until they are synced -- detach_trainer() is the explicit way out.
             trs = [t for t in getattr(self, "_trainers", []) if t is not trainer and type(t) is not type(trainer)]

@@ -23,6 +23,9 @@ ProposalLayer runs inside the training step exactly where the reference runs it 
 region_proposal_network.py:123-126) and its result is discarded, as there; `run_proposal_layer=False` skips it (same gradients).
 """
 
+import contextlib
+import functools
+
 import numpy as np
 
 from . import tuning as _tuning
@@ -67,7 +70,6 @@ def trunk_forward(model, x, fuse_pools=True):
 
 
 def _grad_stream(rt, *arrays):
-    import contextlib
     if _tuning.get("FRCNN_TRAIN_STREAMS") == "1":
         return contextlib.nullcontext()
     return rt.mem.aux_stream("grad", *arrays)
@@ -90,23 +92,14 @@ def trunk_backward(trainer, layer_inputs, g):
             if isinstance(xin, _PoolArg):                             # the pool ran inside its convolution: route by the kept bytes
                 g = rt.maxpool2x2_bwd_idx(xin.idx, g, xin.H, xin.W)
                 continue
-            if getattr(trainer, "keep_dy", None) is not None:        # tests: the pre-pool maps (near-tie windows = where two fp32 passes may route differently)
-                trainer.kept_dy.setdefault("pool_inputs", []).append(xin)
+            trainer._tap_pool(xin)
             g = rt.maxpool2x2_bwd(xin, g)
             continue
         name = l[0]
-        keep = getattr(trainer, "keep_dy", None)
-        if keep is not None and name in keep:                     # tests: the (input, upstream gradient) pair a weight gradient was computed from
-            trainer.kept_dy[name] = (xin, g.clone() if hasattr(g, "clone") else g.copy())
-        # this layer's weight / bias gradient on the gradient stream: it needs (xin, g) only, so it runs NEXT TO the input-gradient
-        # convolution below (FRCNN_TRAIN_STREAMS=1: one stream, A/B hook)
-        with _grad_stream(rt, xin, g):
-            rt.conv_wgrad(xin, g, 3, out=trainer.grad[name + "/W"])
-            rt.bias_grad(g, out=trainer.grad[name + "/b"])
-            if hasattr(trainer, "_grads_ready"):
-                trainer._grads_ready(name)                        # data parallel: a finished bucket starts its all-reduce now
+        trainer._tap(name, xin, g)
+        trainer._param_grads(name, xin, g, rt.conv_wgrad)
         if name != first:                                         # the image needs no gradient
-            if not getattr(trainer, "_dgrad_packed", False):          # (RPNTrainer re-packs every layer in one launch per step)
+            if not trainer._dgrad_packed:                             # (the trainers re-pack every layer in one launch per step)
                 rt.pack_conv_dgrad_w(links[name].Wp, 3, out=trainer.wd[name])
             below = layer_inputs[pos - 1] if pos > 0 else None
             if unpool and below is not None and below[0] == "pool" and isinstance(below[1], _PoolArg):
@@ -121,134 +114,127 @@ def trunk_backward(trainer, layer_inputs, g):
     return g
 
 
-def _conv_dims(trainer, name):
-    link = dict(trainer.convs)[name]
-    return int(link.cin), int(link.cout)
+class _OperandMath(object):
+    """One arithmetic of the operand-form trunk walkers below (trainer.arith; None for the fp32 MFMA step, which has walkers of its own).  In these
+    arithmetics a 3x3 convolution reads an OPERAND tensor -- the 3-way split or the 16-bit image of the fp32 NCHW map -- and weights re-packed into
+    the same form once per step.  A subclass holds exactly what differs: the runtime it runs on, the operand conversion, the convolution and its
+    `want_*` keyword, the first-layer form and the predicate that selects it, the weight-gradient entry, the re-pack entry and the buffer shape.
+    links: [(name, link)] whose forward weights are re-packed (w_fwd); dgrad: those whose input-gradient weights are (w_dgrad).  The trainer
+    passes the convolutions it runs forward / takes an input gradient of; _SplitMath narrows both to the layers it has split weights for."""
+
+    def __init__(self, rt, links, dgrad):
+        self.rt, self.links = rt, links
+        self.w_fwd = {n: rt.mem.empty(self.w_shape(l.cin, l.cout), "i16") for n, l in links}
+        self.w_dgrad = {n: rt.mem.empty(self.w_shape(l.cout, l.cin), "i16") for n, l in dgrad}
+
+    def repack(self):
+        """Operand-form weights of every forward / input-gradient convolution from the current (packed fp32) weights: one launch."""
+        if self.links:
+            self.pack_many([(l.Wp, self.w_fwd[n], self.w_dgrad.get(n), l.cin, l.cout) for n, l in self.links])
 
 
-def trunk_forward_split(trainer, x):
-    """trunk_forward with the 3x3 convolutions (all but the 3-channel first one) computed as six bf16 MFMA products of 3-way split
-    fp32 operands (csrc/conv_f32s.hip): every convolution leaves its result as fp32 NCHW (what the weight-gradient kernel, pooling
-    and the ReLU masks read) and, when a convolution follows, as the split tensor that one reads.  -> (feat, inputs, feat_split)."""
-    model, rt = trainer.model, trainer.rt
-    layers = model.trunk.layers
-    inputs, h, hs = [], x, None
+class _SplitMath(_OperandMath):
+    """conv_math="split": six bf16 MFMA products of 3-way split fp32 operands (csrc/conv_f32s.hip; weight gradients: csrc/train.hip
+    conv_wgrad_f32s_kernel, fp32 NCHW in, the split happens in the kernel).  The 3-channel layers stay outside: they have no split weights, run
+    the fp32 link (or, for conv1_1 in front of a convolution, the first-layer kernel) and get no input gradient."""
+
+    def __init__(self, rt, links, dgrad):
+        big = [(n, l) for n, l in links if int(l.cin) > 3]
+        _OperandMath.__init__(self, rt, big, big)                     # both forms for every cin > 3 layer, not `dgrad`: one launch packs them in pairs
+        self.operand, self.wgrad, self.pack_many = rt.f32s_from_nchw, rt.conv_wgrad_f32s, rt.f32s_pack_many
+
+    def w_shape(self, ci, co):
+        pad = self.rt.bf16_pad
+        return (3, pad(ci) // 16, 9, pad(co), 16)
+
+    def conv(self, x, w, bias, cin, cout, relu, want, **mask):
+        return self.rt.conv3x3_f32s_train(x, w, bias, cin, cout, relu=relu, want_split=want, **mask)
+
+    def first_layer(self, link, idx, layers):
+        return int(link.cin) <= 3 and idx == 0 and int(link.cout) <= 64 and idx + 1 < len(layers) and layers[idx + 1] != "pool"
+
+    def conv1(self, x, link):
+        return self.rt.conv1_f32s_train(x, link.Wp, link.b, link.cout, relu=True)
+
+
+class _HalfMath(_OperandMath):
+    """conv_math / precision "bf16" or "f16": every product on RNE-rounded 16-bit operands with fp32 accumulation (csrc/conv_f32s.hip's one-part
+    form, csrc/train.hip conv_wgrad_f32s_kernel<1>).  rt is the trainer's runtime seen through its operand format (rt.with_half(half)): the fp16
+    twins of every 16-bit entry when half == "f16".  Every layer is re-packed; the first one has no input-gradient weights."""
+
+    def __init__(self, rt, links, dgrad):
+        _OperandMath.__init__(self, rt, links, dgrad)
+        self.operand, self.wgrad, self.pack_many = rt.bf16_from_nchw, rt.conv_wgrad_bf16, rt.bf16_pack_many
+
+    def w_shape(self, ci, co):
+        pad = self.rt.bf16_pad
+        return (pad(ci) // 16, 9, pad(co), 16)
+
+    def conv(self, x, w, bias, cin, cout, relu, want, **mask):
+        return self.rt.conv3x3_bf16_train(x, w, bias, cin, cout, relu=relu, want_bf16=want, **mask)
+
+    def first_layer(self, link, idx, layers):
+        return int(link.cin) <= 3 and int(link.cout) <= 64
+
+    def conv1(self, x, link):                                         # fp32 image and weights rounded in registers
+        return self.rt.conv1_bf16_train(x, link.Wp, link.b, link.cout, relu=True)
+
+
+def trunk_forward_operand(trainer, x):
+    """trunk_forward in an operand-form arithmetic (trainer.arith).  Every convolution leaves its result as fp32 NCHW (what the weight-gradient
+    kernel, pooling and the ReLU masks read) and, when a convolution follows, as the operand tensor that one reads.  Pools run on fp32 and
+    leave no operand.  A layer the arithmetic has no weights for runs its fp32 link.  -> (feat, inputs, feat as operand)."""
+    arith = trainer.arith
+    rt, trunk = arith.rt, trainer.model.trunk
+    layers = trunk.layers
+    inputs, h, hop = [], x, None
     for idx, l in enumerate(layers):
         inputs.append(h)
         if l == "pool":
-            h, hs = rt.maxpool2x2(h), None
+            h, hop = rt.maxpool2x2(h), None
             continue
-        name, link = l[0], model.trunk.links[l[0]]
-        if int(link.cin) <= 3:                                        # conv1_1: the first-layer kernel, fp32 NCHW image in
-            if idx == 0 and int(link.cout) <= 64 and idx + 1 < len(layers) and layers[idx + 1] != "pool":
-                hs, h = rt.conv1_f32s_train(h, link.Wp, link.b, link.cout, relu=True)
-            else:
-                h, hs = link(h, relu=True), None
-            continue
-        if hs is None:
-            hs = rt.f32s_from_nchw(h)
-        conv_next = idx + 1 == len(layers) or layers[idx + 1] != "pool"        # the last map feeds rpn_conv_3x3
-        hs, h = rt.conv3x3_f32s_train(hs, trainer.ws_fwd[name], link.b, link.cin, link.cout, relu=True, want_split=conv_next)
-    if hs is None:
-        hs = rt.f32s_from_nchw(h)                                     # (trunks that end in a pool or in the first layer)
-    return h, inputs, hs
+        name, link = l[0], trunk.links[l[0]]
+        if arith.first_layer(link, idx, layers):                      # conv1_1: the first-layer kernel, fp32 NCHW image in
+            hop, h = arith.conv1(h, link)
+        elif name not in arith.w_fwd:
+            h, hop = link(h, relu=True), None
+        else:
+            if hop is None:
+                hop = arith.operand(h)
+            conv_next = idx + 1 == len(layers) or layers[idx + 1] != "pool"        # the last map feeds rpn_conv_3x3
+            hop, h = arith.conv(hop, arith.w_fwd[name], link.b, link.cin, link.cout, relu=True, want=conv_next)
+    if hop is None:
+        hop = arith.operand(h)                                        # (trunks that end in a pool or in the first layer)
+    return h, inputs, hop
 
 
-def trunk_backward_split(trainer, layer_inputs, g):
-    """trunk_backward with the input-gradient convolutions on split tensors; weight and bias gradients as before (fp32 NCHW)."""
-    rt = trainer.rt
+def trunk_backward_operand(trainer, layer_inputs, g):
+    """trunk_backward in an operand-form arithmetic: the input-gradient convolutions on the operand form of the upstream gradient and of the
+    rotated weights with the ReLU mask fused, weight gradients by the arithmetic's own entry (fp32 NCHW in), bias gradients and pools in fp32.
+    A layer has an input gradient when it is not the trunk's first and the arithmetic keeps input-gradient weights for it."""
+    arith = trainer.arith
+    rt = arith.rt
     first = trainer.convs[0][0]
     links = dict(trainer.convs)
     names = [l if l == "pool" else l[0] for l, _ in layer_inputs]
-    gs = None
+    dgrad = set(arith.w_dgrad) - {first}                              # the layers with an input gradient
+    gop = None
     for pos in range(len(layer_inputs) - 1, -1, -1):
         l, xin = layer_inputs[pos]
         if l == "pool":
-            if getattr(trainer, "keep_dy", None) is not None:
-                trainer.kept_dy.setdefault("pool_inputs", []).append(xin)
-            g, gs = rt.maxpool2x2_bwd(xin, g), None
+            trainer._tap_pool(xin)
+            g, gop = rt.maxpool2x2_bwd(xin, g), None
             continue
         name = l[0]
-        keep = getattr(trainer, "keep_dy", None)
-        if keep is not None and name in keep:
-            trainer.kept_dy[name] = (xin, g.clone() if hasattr(g, "clone") else g.copy())
-        with _grad_stream(rt, xin, g):                               # next to the input-gradient convolution below (see trunk_backward)
-            rt.conv_wgrad_f32s(xin, g, out=trainer.grad[name + "/W"])  # split products too: fp32 NCHW in, the split happens in the kernel
-            rt.bias_grad(g, out=trainer.grad[name + "/b"])
-            if hasattr(trainer, "_grads_ready"):
-                trainer._grads_ready(name)
-        if name == first:
+        trainer._tap(name, xin, g)
+        trainer._param_grads(name, xin, g, arith.wgrad)                # next to the input-gradient convolution below (see trunk_backward)
+        if name not in dgrad:
             continue                                                  # the image needs no gradient
-        cin, cout = _conv_dims(trainer, name)
-        if cin <= 3:
-            continue
-        if gs is None:
-            gs = rt.f32s_from_nchw(g)
-        below = names[pos - 1] if pos > 0 else None                   # who consumes dL/d(input): a convolution with an input gradient of its own?
-        below_conv = below is not None and below != "pool" and below != first and _conv_dims(trainer, below)[0] > 3
-        gs, g = rt.conv3x3_f32s_train(gs, trainer.ws_dgrad[name], trainer.zero_bias, cout, cin, relu=False, want_split=below_conv, mask=xin)
-    rt.mem.join_aux_stream("grad")
-    return g
-
-
-def trunk_forward_bf16(trainer, x):
-    """trunk_forward with every convolution on bf16 operands and fp32 accumulation (RPNTrainer(conv_math="bf16")): conv1_1 on the
-    first-layer kernel (fp32 image and weights rounded in registers), the others on csrc/conv_f32s.hip's one-part form.  Every
-    convolution leaves its result as fp32 NCHW (what the weight gradient, pooling and the ReLU masks read) and, when a convolution
-    follows, as the blocked bf16 tensor RNE(fp32) that one reads.  Pools run on fp32.  -> (feat, inputs, feat_bf16)."""
-    model = trainer.model
-    rt = rtb = trainer.rt.with_half(getattr(trainer, "half", "bf16"))      # "f16" (RPNTrainer(conv_math="f16")): the fp16 twins of every 16-bit entry
-    layers = model.trunk.layers
-    inputs, h, hb = [], x, None
-    for idx, l in enumerate(layers):
-        inputs.append(h)
-        if l == "pool":
-            h, hb = rt.maxpool2x2(h), None
-            continue
-        name, link = l[0], model.trunk.links[l[0]]
-        if int(link.cin) <= 3 and int(link.cout) <= 64:              # conv1_1: the first-layer kernel, fp32 NCHW image in
-            hb, h = rt.conv1_bf16_train(h, link.Wp, link.b, link.cout, relu=True)
-            continue
-        if hb is None:
-            hb = rtb.bf16_from_nchw(h)
-        conv_next = idx + 1 == len(layers) or layers[idx + 1] != "pool"        # the last map feeds rpn_conv_3x3
-        hb, h = rt.conv3x3_bf16_train(hb, trainer.wb_fwd[name], link.b, link.cin, link.cout, relu=True, want_bf16=conv_next)
-    if hb is None:
-        hb = rtb.bf16_from_nchw(h)                                    # (trunks that end in a pool)
-    return h, inputs, hb
-
-
-def trunk_backward_bf16(trainer, layer_inputs, g):
-    """trunk_backward_split on bf16 operands: input-gradient convolutions on RNE(upstream gradient) and RNE(rotated weights) with the
-    ReLU mask fused, weight gradients on RNE(x), RNE(dy) (csrc/train.hip conv_wgrad_f32s_kernel<1>), bias gradients and pools in fp32."""
-    rt = rtb = trainer.rt.with_half(getattr(trainer, "half", "bf16"))
-    first = trainer.convs[0][0]
-    names = [l if l == "pool" else l[0] for l, _ in layer_inputs]
-    gb = None
-    for pos in range(len(layer_inputs) - 1, -1, -1):
-        l, xin = layer_inputs[pos]
-        if l == "pool":
-            if getattr(trainer, "keep_dy", None) is not None:
-                trainer.kept_dy.setdefault("pool_inputs", []).append(xin)
-            g, gb = rt.maxpool2x2_bwd(xin, g), None
-            continue
-        name = l[0]
-        keep = getattr(trainer, "keep_dy", None)
-        if keep is not None and name in keep:
-            trainer.kept_dy[name] = (xin, g.clone() if hasattr(g, "clone") else g.copy())
-        with _grad_stream(rt, xin, g):                               # next to the input-gradient convolution below (see trunk_backward)
-            rt.conv_wgrad_bf16(xin, g, out=trainer.grad[name + "/W"])
-            rt.bias_grad(g, out=trainer.grad[name + "/b"])
-            if hasattr(trainer, "_grads_ready"):
-                trainer._grads_ready(name)
-        if name == first:
-            continue                                                  # the image needs no gradient
-        cin, cout = _conv_dims(trainer, name)
-        if gb is None:
-            gb = rtb.bf16_from_nchw(g)
-        below = names[pos - 1] if pos > 0 else None                   # who consumes dL/d(input): a convolution with an input gradient of its own?
-        below_conv = below is not None and below != "pool" and below != first
-        gb, g = rt.conv3x3_bf16_train(gb, trainer.wb_dgrad[name], trainer.zero_bias, cout, cin, relu=False, want_bf16=below_conv, mask=xin)
+        if gop is None:
+            gop = arith.operand(g)
+        cin, cout = int(links[name].cin), int(links[name].cout)
+        below_conv = pos > 0 and names[pos - 1] in dgrad               # who consumes dL/d(input): a convolution with an input gradient of its own?
+        gop, g = arith.conv(gop, arith.w_dgrad[name], trainer.zero_bias, cout, cin, relu=False, want=below_conv, mask=xin)
     rt.mem.join_aux_stream("grad")
     return g
 
@@ -263,7 +249,7 @@ class _ResNetTrunk(object):
     parameters, their adoption into the arena, forward-with-tape and backward, and the layout conversions of a flat buffer.  Segment keys are
     the link paths below `trunk/` (`conv1/W`, `bn1/gamma`, `res3/a/conv4/W`, ...); a W segment holds the convolution kernels' packed layout.
     The buffer is laid out in EXECUTION order -- a block's projection shortcut conv4 before its conv1 -- so the backward pass fills it from
-    the end and _BucketedAllReduce's tail buckets close as they do for VGG."""
+    the end and the all-reduce's tail buckets close as they do for VGG."""
 
     def __init__(self, trunk):
         from .models.resnet import conv_specs
@@ -332,60 +318,6 @@ class _Seg(object):
         self.size = int(np.prod(shape))
 
 
-class _ParamArena(object):
-    """A trainer keeps its parameters in ONE flat buffer (self.W) and re-points the links' arrays at windows of it, so a single
-    fused launch updates everything.  Two trainers on one model (the reference's rpn -> rcnn -> rpn alternation, train.py; the
-    hidden RCNNTrainer of FasterRCNN.__call__) would orphan each other's windows: before every step a trainer therefore checks
-    that each link still points INTO its buffer and re-adopts the link's current values if not (velocities are kept)."""
-
-    def _adopt(self, key, current):
-        seg = self.seg[key]
-        v = self.rt.mem.view(self.W, seg.offset, seg.shape)
-        if not self.rt.mem.within(current, self.W):
-            v[...] = current
-        return v
-
-    def _ensure_adopted(self):
-        raise NotImplementedError
-
-    # ------------------------------------------------------------------ the update rule (utils/prepare_train.py:146-167 get_optimizer)
-    def _init_optimizer(self, who, opt, opt_args, weight_decay):
-        """Validate `opt` / `opt_args` and set the rule's hyper-parameters as plain attributes (read at every update(), like self.lr)."""
-        if opt not in OPT_DEFAULTS:
-            raise ValueError("%s: opt must be one of %s, not %r" % (who, sorted(OPT_DEFAULTS), opt))
-        args = dict(opt_args or {})
-        unknown = set(args) - set(OPT_DEFAULTS[opt])
-        if unknown:
-            raise ValueError("%s: opt=%r has no hyper-parameter %s (it takes %s)" % (who, opt, sorted(unknown), sorted(OPT_DEFAULTS[opt])))
-        for k, v in dict(OPT_DEFAULTS[opt], **args).items():
-            setattr(self, k, v)
-        if opt != "MomentumSGD" and not float(self.eps) > 0:
-            raise ValueError("%s: eps must be positive (the zero padding of the parameter buffer would compute 0 / 0), not %r" % (who, self.eps))
-        self.opt = opt
-        # train_rpn.py:167 hooks WeightDecay(0.0005) onto MomentumSGD only; an explicit value is honoured by every rule
-        self.weight_decay = (0.0005 if opt == "MomentumSGD" else 0.0) if weight_decay is None else weight_decay
-
-    def _alloc_optimizer_state(self):
-        """The rule's state: one or two zero-initialised arenas in self.W's layout (self.moments: Chainer's state name -> buffer) and, for
-        Adam, the device-resident step count / bias correction (self.opt_state)."""
-        rt = self.rt
-        self.moments = {k: rt.mem.zeros((self.n_flat,), "f32") for k in OPT_STATE_KEYS[self.opt]}
-        self.V = self.moments["v"] if self.opt == "MomentumSGD" else None      # MomentumSGD's velocities
-        self.opt_state = AdamState(rt) if self.opt == "Adam" else None
-
-    def _optimizer_step(self, scaler_state=None):
-        """Adam / AdaGrad / RMSprop over the flat buffers (csrc/optimizer.hip); with a loss scaler's state on G / S, or nothing when its flag is set."""
-        rt, mo = self.rt, self.moments
-        if self.opt == "Adam":
-            rt.opt_step("Adam", self.W, self.G, mo["m"], mo["v"], lr=self.alpha, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
-                        weight_decay=self.weight_decay, opt_state=self.opt_state.buf, scaler_state=scaler_state)
-        elif self.opt == "AdaGrad":
-            rt.opt_step("AdaGrad", self.W, self.G, mo["h"], lr=self.lr, eps=self.eps, weight_decay=self.weight_decay, scaler_state=scaler_state)
-        else:
-            rt.opt_step("RMSprop", self.W, self.G, mo["ms"], lr=self.lr, beta1=self.alpha, eps=self.eps, weight_decay=self.weight_decay,
-                        scaler_state=scaler_state)
-
-
 # Chainer's defaults (optimizers.Adam / AdaGrad / RMSprop); MomentumSGD's lr and momentum are the trainers' own arguments
 OPT_DEFAULTS = {"MomentumSGD": {}, "Adam": dict(alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8), "AdaGrad": dict(lr=1e-3, eps=1e-8),
                 "RMSprop": dict(lr=1e-2, alpha=0.99, eps=1e-8)}
@@ -421,50 +353,6 @@ class AdamState(object):
         for _ in range(int(t)):
             p = p * float(beta)
         return p
-
-
-class _BucketedAllReduce(_ParamArena):
-    """Data parallel: the gradient all-reduce as a few contiguous TAIL buckets of the flat buffer, each launched asynchronously
-    the moment the layer that completes it has its gradient kernels enqueued (the buffer is laid out in forward order and the
-    backward pass fills it from the end), so the exchange runs under the rest of the backward pass.  Same element-wise sums over
-    ranks as one all-reduce.  Few large buckets, not many small ones: xGMI is point-to-point, a ring collective is per-link bound,
-    and every extra collective adds its latency."""
-
-    def _plan_buckets(self, names, n_buckets=3):
-        """names: parameter groups in FORWARD (= buffer) order; every group's gradients precede, in time, those of the groups
-        before it.  Buckets are (closing group, start, end) in backward order and tile [0, n_flat)."""
-        total, end = self.n_flat, self.n_flat
-        target = total / float(n_buckets)
-        self.buckets = []
-        for i in range(len(names) - 1, -1, -1):
-            start = self.seg[names[i] + "/W"].offset
-            if end - start >= target or i == 0:
-                self.buckets.append((names[i], start if i else 0, end))
-                end = start
-        self._closing = {b[0]: k for k, b in enumerate(self.buckets)}
-        self._works = []
-
-    def _grads_ready(self, name):
-        k = self._closing.get(name)
-        if k is None or self.comm is None or not getattr(self.comm, "active", self.comm.world_size > 1):
-            return
-        _, start, end = self.buckets[k]
-        self._works.append(self.comm.all_reduce_sum_async(self.G[start:end]))
-
-    def _drain(self):
-        for w in self._works:
-            self.comm.wait(w)
-        self._works = []
-
-    def all_reduce(self):
-        """Sum the gradient buffer over the replicas (ParallelUpdater: grads are added, not averaged).  The buckets were launched
-        during the backward pass (_grads_ready); this waits for them -- the update must see every sum."""
-        if self.comm is None or not getattr(self.comm, "active", self.comm.world_size > 1):
-            return
-        complete = len(self._works) == len(self.buckets)
-        self._drain()
-        if not complete:                                          # forward_backward was not the producer (e.g. a hand-filled G)
-            self.comm.all_reduce_sum(self.G)
 
 
 def _is_pow2(v):
@@ -541,7 +429,265 @@ class LossScaler(object):
         self.buf[...] = self.rt.mem.from_numpy(w)
 
 
-class RPNTrainer(_BucketedAllReduce):
+def _packed_to_chainer(wp, link):
+    """A 3x3 convolution's weights, the kernels' packed layout (Cin*9, Cout) -> Chainer's (Cout, Cin, 3, 3) (host arrays)."""
+    return np.ascontiguousarray(wp.T).reshape(link.cout, link.cin, 3, 3)
+
+
+def _chainer_to_packed(w, link):
+    return np.asarray(w, dtype=np.float32).reshape(link.cout, -1).T
+
+
+class _Trainer(object):
+    """What RPNTrainer and RCNNTrainer share: the parameter arena, the bucketed gradient all-reduce, the buffers of the step's arithmetic, the
+    update, and the trunk-convolution half of the layout conversions.  A subclass sets model, rt, comm, layers and convs ([(name, link)] of the
+    3x3 convolutions it trains, forward order), lays out its arena (_build_arena), picks its arithmetic (_init_arithmetic) and plans its buckets.
+
+    The arena: a trainer keeps its parameters in ONE flat buffer (self.W) and re-points the links' arrays at windows of it, so a single
+    fused launch updates everything.  Two trainers on one model (the reference's rpn -> rcnn -> rpn alternation, train.py; the
+    hidden RCNNTrainer of FasterRCNN.__call__) would orphan each other's windows: before every step a trainer therefore checks
+    that each link still points INTO its buffer and re-adopts the link's current values if not (velocities are kept).
+
+    Data parallel: the gradient all-reduce as a few contiguous TAIL buckets of the flat buffer, each launched asynchronously
+    the moment the layer that completes it has its gradient kernels enqueued (the buffer is laid out in forward order and the
+    backward pass fills it from the end), so the exchange runs under the rest of the backward pass.  Same element-wise sums over
+    ranks as one all-reduce.  Few large buckets, not many small ones: xGMI is point-to-point, a ring collective is per-link bound,
+    and every extra collective adds its latency.
+    comm: None (one replica) or a TorchComm-like object: all_reduce_sum, all_reduce_sum_async, wait, and the attribute `active` -- False is
+    the one way a communicator says "skip the exchange" (TorchComm: a single rank that was not forced)."""
+
+    keep_dy = None              # tests: a set of layer names -> the step records what _tap() sees into kept_dy (and runs its pools unfused)
+    kept_dy = None
+    _dgrad_packed = False       # True between the step's one-launch re-pack of the input-gradient weights and the end of its backward pass
+    arith = None                # the operand-form arithmetic (_OperandMath); None: fp32 MFMA convolutions
+
+    def _build_arena(self, segments):
+        """segments: [(key, shape)] in buffer order -> seg, n_flat, one flat buffer each for parameters (W), gradients (G) and the rule's state
+        (moments), the links adopted into W, and grad: a view of G per segment.  Every segment is 256-byte aligned."""
+        rt = self.rt
+        self.seg, off = {}, 0
+        for key, shape in segments:
+            self.seg[key] = _Seg(key, shape, off)
+            off += (self.seg[key].size + 63) // 64 * 64
+        self.n_flat = off
+        self.W = rt.mem.zeros((off,), "f32")
+        self.G = rt.mem.zeros((off,), "f32")
+        self._alloc_optimizer_state()
+        self._ensure_adopted()
+        self.grad = {k: rt.mem.view(self.G, s.offset, s.shape) for k, s in self.seg.items()}
+
+    def _conv_segments(self):
+        return [(name + sfx, arr.shape) for name, link in self.convs for sfx, arr in (("/W", link.Wp), ("/b", link.b))]
+
+    def _adopt(self, key, current):
+        seg = self.seg[key]
+        v = self.rt.mem.view(self.W, seg.offset, seg.shape)
+        if not self.rt.mem.within(current, self.W):
+            v[...] = current
+        return v
+
+    def _adopt_convs(self):
+        for name, link in self.convs:
+            link.Wp = self._adopt(name + "/W", link.Wp)
+            link.b = self._adopt(name + "/b", link.b)
+            link._adopted = True
+
+    def _ensure_adopted(self):
+        raise NotImplementedError
+
+    def _init_arithmetic(self, arithmetic, loss_scale, fwd, dgrad):
+        """The buffers of the step's arithmetic ("mfma", "split", "bf16" or "f16").  fwd / dgrad: [(name, link)] of the 3x3 convolutions whose
+        forward pass / input gradient the trainer runs.  Always: wd, the weights of the fp32 input-gradient convolutions (re-packed from the
+        current weights every step).  split / 16-bit: self.arith and its re-packed weights (ws_* / wb_*: only a trainer that uses them has the
+        attribute).  f16: the device-side loss scale from `loss_scale` -- None = "dynamic", a power of two, or a dict of LossScaler's arguments."""
+        rt = self.rt
+        self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32") for name, link in dgrad}
+        self.half = "f16" if arithmetic == "f16" else "bf16"          # the 16-bit operand format of the mixed-precision step
+        if arithmetic == "split":
+            self.arith = _SplitMath(rt, fwd, dgrad)
+            self.ws_fwd, self.ws_dgrad = self.arith.w_fwd, self.arith.w_dgrad
+        elif arithmetic in ("bf16", "f16"):
+            # one view for the trainer's life: with_half copies the runtime's attributes as they are NOW, so one re-bound on self.rt later is not seen
+            self.arith = _HalfMath(rt.with_half(self.half), fwd, dgrad)
+            self.wb_fwd, self.wb_dgrad = self.arith.w_fwd, self.arith.w_dgrad
+        self.loss_scaler = None
+        if arithmetic == "f16":
+            kw = dict(loss_scale) if isinstance(loss_scale, dict) else {"loss_scale": "dynamic" if loss_scale is None else loss_scale}
+            self.loss_scaler = LossScaler(rt, **kw)
+            self._g_scale_word = 0                                    # which state word holds the scale self.G is multiplied by
+
+    # ------------------------------------------------------------------ backward-pass helpers of every trunk walker and of the trainers' own layers
+    def _tap(self, name, xin, g):
+        """tests (keep_dy set): the (input, upstream gradient) pair a layer's weight gradient is computed from"""
+        if self.keep_dy is not None and name in self.keep_dy:
+            self.kept_dy[name] = (xin, g.clone() if hasattr(g, "clone") else g.copy())      # hasattr: a torch tensor or the emulator's NumPy array
+
+    def _tap_pool(self, xin):
+        """tests (keep_dy set): the pre-pool maps (near-tie windows = where two fp32 passes may route differently)"""
+        if self.keep_dy is not None:
+            self.kept_dy.setdefault("pool_inputs", []).append(xin)
+
+    def _param_grads(self, name, xin, g, wgrad, ready=True):
+        """A convolution's weight / bias gradient from (input, upstream gradient), on the gradient stream: they need (xin, g) only, so they run
+        NEXT TO the input-gradient convolution the caller launches next (FRCNN_TRAIN_STREAMS=1: one stream, A/B hook).  wgrad: the
+        arithmetic's weight-gradient entry, (xin, g, out=...) of a 3x3 convolution.
+        ready: data parallel -- a bucket that `name` closes starts its all-reduce now."""
+        rt = self.rt
+        with _grad_stream(rt, xin, g):
+            wgrad(xin, g, out=self.grad[name + "/W"])
+            rt.bias_grad(g, out=self.grad[name + "/b"])
+            if ready:
+                self._grads_ready(name)
+
+    # ------------------------------------------------------------------ the update rule (utils/prepare_train.py:146-167 get_optimizer)
+    def _init_optimizer(self, who, opt, opt_args, weight_decay):
+        """Validate `opt` / `opt_args` and set the rule's hyper-parameters as plain attributes (read at every update(), like self.lr)."""
+        if opt not in OPT_DEFAULTS:
+            raise ValueError("%s: opt must be one of %s, not %r" % (who, sorted(OPT_DEFAULTS), opt))
+        args = dict(opt_args or {})
+        unknown = set(args) - set(OPT_DEFAULTS[opt])
+        if unknown:
+            raise ValueError("%s: opt=%r has no hyper-parameter %s (it takes %s)" % (who, opt, sorted(unknown), sorted(OPT_DEFAULTS[opt])))
+        for k, v in dict(OPT_DEFAULTS[opt], **args).items():
+            setattr(self, k, v)
+        if opt != "MomentumSGD" and not float(self.eps) > 0:
+            raise ValueError("%s: eps must be positive (the zero padding of the parameter buffer would compute 0 / 0), not %r" % (who, self.eps))
+        self.opt = opt
+        # train_rpn.py:167 hooks WeightDecay(0.0005) onto MomentumSGD only; an explicit value is honoured by every rule
+        self.weight_decay = (0.0005 if opt == "MomentumSGD" else 0.0) if weight_decay is None else weight_decay
+
+    def _alloc_optimizer_state(self):
+        """The rule's state: one or two zero-initialised arenas in self.W's layout (self.moments: Chainer's state name -> buffer) and, for
+        Adam, the device-resident step count / bias correction (self.opt_state)."""
+        rt = self.rt
+        self.moments = {k: rt.mem.zeros((self.n_flat,), "f32") for k in OPT_STATE_KEYS[self.opt]}
+        self.V = self.moments["v"] if self.opt == "MomentumSGD" else None      # MomentumSGD's velocities
+        self.opt_state = AdamState(rt) if self.opt == "Adam" else None
+
+    def _optimizer_step(self, scaler_state=None):
+        """Adam / AdaGrad / RMSprop over the flat buffers (csrc/optimizer.hip); with a loss scaler's state on G / S, or nothing when its flag is set."""
+        rt, mo = self.rt, self.moments
+        if self.opt == "Adam":
+            rt.opt_step("Adam", self.W, self.G, mo["m"], mo["v"], lr=self.alpha, beta1=self.beta1, beta2=self.beta2, eps=self.eps,
+                        weight_decay=self.weight_decay, opt_state=self.opt_state.buf, scaler_state=scaler_state)
+        elif self.opt == "AdaGrad":
+            rt.opt_step("AdaGrad", self.W, self.G, mo["h"], lr=self.lr, eps=self.eps, weight_decay=self.weight_decay, scaler_state=scaler_state)
+        else:
+            rt.opt_step("RMSprop", self.W, self.G, mo["ms"], lr=self.lr, beta1=self.alpha, eps=self.eps, weight_decay=self.weight_decay,
+                        scaler_state=scaler_state)
+
+    def update(self):
+        self._ensure_adopted()
+        if self.loss_scaler is not None:
+            # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
+            self.loss_scaler.check(self.G)
+            if self.opt == "MomentumSGD":
+                self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
+            else:                                                     # (Adam: one more one-lane launch, which counts the step unless it is skipped)
+                self._optimizer_step(self.loss_scaler.buf)
+            self.loss_scaler.update()
+            self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
+        elif self.opt == "MomentumSGD":
+            self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
+        else:
+            self._optimizer_step()
+        self.model.mark_params_updated(self)
+        self.iteration += 1
+
+    # ------------------------------------------------------------------ data parallel
+    def _comm_active(self):
+        return self.comm is not None and self.comm.active
+
+    def _plan_buckets(self, names, n_buckets=3):
+        """names: parameter groups in FORWARD (= buffer) order; every group's gradients precede, in time, those of the groups
+        before it.  Buckets are (closing group, start, end) in backward order and tile [0, n_flat)."""
+        total, end = self.n_flat, self.n_flat
+        target = total / float(n_buckets)
+        self.buckets = []
+        for i in range(len(names) - 1, -1, -1):
+            start = self.seg[names[i] + "/W"].offset
+            if end - start >= target or i == 0:
+                self.buckets.append((names[i], start if i else 0, end))
+                end = start
+        self._closing = {b[0]: k for k, b in enumerate(self.buckets)}
+        self._works = []
+
+    def _grads_ready(self, name):
+        k = self._closing.get(name)
+        if k is None or not self._comm_active():
+            return
+        _, start, end = self.buckets[k]
+        self._works.append(self.comm.all_reduce_sum_async(self.G[start:end]))
+
+    def _drain(self):
+        for w in self._works:
+            self.comm.wait(w)
+        self._works = []
+
+    def all_reduce(self):
+        """Sum the gradient buffer over the replicas (ParallelUpdater: grads are added, not averaged).  The buckets were launched
+        during the backward pass (_grads_ready); this waits for them -- the update must see every sum."""
+        if not self._comm_active():
+            return
+        complete = len(self._works) == len(self.buckets)
+        self._drain()
+        if not complete:                                          # forward_backward was not the producer (e.g. a hand-filled G)
+            self.comm.all_reduce_sum(self.G)
+
+    # ------------------------------------------------------------------ layouts: the trunk-convolution half; the subclasses add what else they train
+    def sync_params(self):
+        """Packed training weights -> Chainer-layout arrays on the links (for snapshots / inference objects)."""
+        for name, link in self.convs:
+            link.W = self.rt.transpose(link.Wp).reshape(link.cout, link.cin, 3, 3)
+
+    def _segment_reader(self, flat):
+        """seg(key): the host copy of one segment of a flat buffer in this trainer's layout, in the segment's shape"""
+        host = self.rt.mem.to_numpy(flat)
+
+        def seg(key):
+            sg = self.seg[key]
+            return host[sg.offset:sg.offset + sg.size].reshape(sg.shape)
+        return seg
+
+    @contextlib.contextmanager
+    def _segment_writer(self, flat):
+        """put(key, value) into a host copy of `flat`, which goes back to the device on exit"""
+        host = self.rt.mem.to_numpy(flat).copy()
+
+        def put(key, val):
+            sg = self.seg[key]
+            host[sg.offset:sg.offset + sg.size] = np.asarray(val, dtype=np.float32).reshape(-1)
+        yield put
+        flat[...] = self.rt.mem.from_numpy(host)
+
+    @staticmethod
+    def _conv_path(name):
+        return ("RPN/" if name == "rpn_conv_3x3" else "trunk/") + name
+
+    def _convs_to_chainer(self, seg, out):
+        for name, link in self.convs:
+            out[self._conv_path(name) + "/W"] = _packed_to_chainer(seg(name + "/W"), link)
+            out[self._conv_path(name) + "/b"] = seg(name + "/b").copy()
+
+    def _convs_from_chainer(self, arrays, put):
+        for name, link in self.convs:
+            path = self._conv_path(name)
+            if path + "/W" in arrays:
+                put(name + "/W", _chainer_to_packed(arrays[path + "/W"], link))
+            if path + "/b" in arrays:
+                put(name + "/b", arrays[path + "/b"])
+
+    def grads_chainer_layout(self):
+        """{link path: gradient in Chainer's layout} (host arrays) -- for tests and inspection.  An fp16 trainer returns UNSCALED gradients:
+        the raw buffer self.G holds S times the gradient (S = the loss scale of the step that filled it); the division is exact."""
+        out = self.flat_to_chainer_layout(self.G)
+        if self.loss_scaler is not None:
+            s = np.float32(self.loss_scaler._words()[1][self._g_scale_word])
+            out = {k: v / s for k, v in out.items()}
+        return out
+
+
+class RPNTrainer(_Trainer):
     def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=None, comm=None, run_proposal_layer=True, conv_math="mfma", loss_scale=None,
                  opt="MomentumSGD", opt_args=None):
         """conv_math: "mfma" = forward and input-gradient convolutions on the fp32 MFMA kernel; "split" = the same fp32 convolutions as
@@ -581,50 +727,14 @@ class RPNTrainer(_BucketedAllReduce):
         # (a ResNet trunk's parameters are not `links`: self.resnet lays them out, and rpn_conv_3x3 is the only conv link of this list)
         self.layers = model.trunk.layers if self.resnet is None else []
         self.convs = [(l[0], model.trunk.links[l[0]]) for l in self.layers if l != "pool"] + [("rpn_conv_3x3", rpn.rpn_conv_3x3)]
-        # ---- one flat buffer each for parameters, gradients, velocities; every segment 256-byte aligned
-        segs, off = [], 0
-        def add(name, shape):
-            nonlocal off
-            s = _Seg(name, shape, off)
-            segs.append(s)
-            off += (s.size + 63) // 64 * 64
-            return s
-        self.seg = {}
-        if self.resnet is not None:
-            for key, shape in self.resnet.segments():
-                self.seg[key] = add(key, shape)
-        for name, link in self.convs:
-            self.seg[name + "/W"] = add(name + "/W", link.Wp.shape)
-            self.seg[name + "/b"] = add(name + "/b", link.b.shape)
+        # ---- one flat buffer each for parameters, gradients, velocities: the ResNet trunk, the 3x3 convolutions, the stacked heads
         wp, bp, self.A = rpn._heads_packed
-        self.seg["heads/W"] = add("heads/W", wp.shape)
-        self.seg["heads/b"] = add("heads/b", bp.shape)
-        self.n_flat = off
-        self.W = rt.mem.zeros((off,), "f32")
-        self.G = rt.mem.zeros((off,), "f32")
-        self._alloc_optimizer_state()
-        self._ensure_adopted()
-        self.grad = {k: rt.mem.view(self.G, s.offset, s.shape) for k, s in self.seg.items()}
-        # weights of the input-gradient convolutions (re-packed from the current weights every step)
-        self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32")
-                   for name, link in (self.convs[1:] if self.resnet is None else self.convs)}       # (VGG's first layer needs no input gradient)
+        self._build_arena((self.resnet.segments() if self.resnet is not None else []) + self._conv_segments()
+                          + [("heads/W", wp.shape), ("heads/b", bp.shape)])
+        # (VGG's first layer needs no input gradient)
+        self._init_arithmetic(conv_math, loss_scale, fwd=self.convs, dgrad=self.convs[1:] if self.resnet is None else self.convs)
         self.wd_heads = rt.mem.empty((int(wp.shape[1]), int(wp.shape[0])), "f32")
         self.zero_bias = rt.mem.zeros((512 if self.resnet is None else max(512, int(rpn.rpn_conv_3x3.cin)),), "f32")
-        if conv_math == "split":                                      # split weights of the forward / input-gradient convolutions (re-packed every step)
-            pad = rt.bf16_pad
-            big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
-            self.ws_fwd = {n: rt.mem.empty((3, pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in big}
-            self.ws_dgrad = {n: rt.mem.empty((3, pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in big}
-        self.half = "f16" if conv_math == "f16" else "bf16"           # the 16-bit operand format of the mixed-precision step
-        self.loss_scaler = None
-        if conv_math == "f16":
-            kw = dict(loss_scale) if isinstance(loss_scale, dict) else {"loss_scale": "dynamic" if loss_scale is None else loss_scale}
-            self.loss_scaler = LossScaler(rt, **kw)
-            self._g_scale_word = 0                                    # which state word holds the scale self.G is multiplied by
-        if conv_math in ("bf16", "f16"):                              # 16-bit weights of the forward / input-gradient convolutions (re-packed every step)
-            pad = rt.bf16_pad
-            self.wb_fwd = {n: rt.mem.empty((pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in self.convs}
-            self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
         self._draw = None
         self.iteration = 0
         self._plan_buckets((self.resnet.names if self.resnet is not None else []) + [n for n, _ in self.convs])       # heads follow rpn_conv_3x3 in the buffer and precede it in time
@@ -633,10 +743,7 @@ class RPNTrainer(_BucketedAllReduce):
         rpn = self.model.RPN
         if self.resnet is not None:
             self.resnet.adopt(self)
-        for name, link in self.convs:
-            link.Wp = self._adopt(name + "/W", link.Wp)
-            link.b = self._adopt(name + "/b", link.b)
-            link._adopted = True
+        self._adopt_convs()
         wp, bp, A = rpn._heads_packed
         rpn._heads_packed = (self._adopt("heads/W", wp), self._adopt("heads/b", bp), A)
         rpn._heads_adopted = True
@@ -663,19 +770,11 @@ class RPNTrainer(_BucketedAllReduce):
         with rt.mem.early_stream(unwrap(gt_boxes)):                   # its own stream: it must not wait for the previous step's backward
             labels, targets, inds, n_in, _ = self.atl.forward_device(H, W, gt_boxes, im_h, im_w)      # (host ground truth; a DEVICE array is waited for)
         rt.mem.join_early_stream(labels, targets, inds)
-        if self.conv_math == "split":
-            # split weights of every forward / input-gradient convolution from the current (packed fp32) weights: one launch
-            rt.f32s_pack_many([(l.Wp, self.ws_fwd[n], self.ws_dgrad[n], l.cin, l.cout) for n, l in self.convs if int(l.cin) > 3])
-            feat, inputs, feat_split = trunk_forward_split(self, x)
+        if self.arith is not None:
+            self.arith.repack()
+            feat, inputs, feat_op = trunk_forward_operand(self, x)
             link = rpn.rpn_conv_3x3
-            _, mid = rt.conv3x3_f32s_train(feat_split, self.ws_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_split=False)
-        elif self.conv_math in ("bf16", "f16"):
-            # 16-bit weights of every forward / input-gradient convolution from the current fp32 master weights: one launch
-            rth = rt.with_half(self.half)
-            rth.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs])
-            feat, inputs, feat_b = trunk_forward_bf16(self, x)
-            link = rpn.rpn_conv_3x3
-            _, mid = rth.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want_bf16=False)
+            _, mid = self.arith.conv(feat_op, self.arith.w_fwd["rpn_conv_3x3"], link.b, link.cin, link.cout, relu=True, want=False)
         elif self.resnet is not None:
             # train-mode BatchNormalization trunk: the forward pass keeps its own tape; its input-gradient packings are rebuilt after an update
             rt.pack_conv_dgrad_w_many([(rpn.rpn_conv_3x3.Wp, self.wd["rpn_conv_3x3"], 3), (rpn._heads_packed[0], self.wd_heads, 1)])
@@ -689,10 +788,10 @@ class RPNTrainer(_BucketedAllReduce):
                 with _grad_stream(rt):                                # on the gradient stream: under the forward pass, joined before the backward pass
                     rt.pack_conv_dgrad_w_many([(l.Wp, self.wd[n], 3) for n, l in self.convs[1:]] + [(rpn._heads_packed[0], self.wd_heads, 1)])
                 self._dgrad_packed = True
-            feat, inputs = trunk_forward(model, x, fuse_pools=getattr(self, "keep_dy", None) is None)     # keeps every layer's input
+            feat, inputs = trunk_forward(model, x, fuse_pools=self.keep_dy is None)     # keeps every layer's input
             mid = rpn.rpn_conv_3x3(feat, relu=True)
         score, prob, bbox = rt.rpn_heads(mid, rpn._heads_packed)
-        if getattr(self, "keep_dy", None) is not None:               # tests: every activation map a ReLU / max-pool decision was taken on
+        if self.keep_dy is not None:                                 # tests: every activation map a ReLU / max-pool decision was taken on
             self.kept_dy["rpn_mid"] = mid
             self.kept_dy["layer_inputs"] = list(inputs) + [feat]
         if self.run_proposal_layer:
@@ -715,18 +814,13 @@ class RPNTrainer(_BucketedAllReduce):
             self._g_scale_word = 0
         # ---- backward: heads (one 1x1 convolution over the stacked cls|bbox matrix)
         rt.mem.join_aux_stream("grad")                               # the re-packed input-gradient weights are ready
-        with _grad_stream(rt, mid, draw):
-            rt.conv_wgrad(mid, draw, 1, out=self.grad["heads/W"])
-            rt.bias_grad(draw, out=self.grad["heads/b"])
-        if not getattr(self, "_dgrad_packed", False):
+        self._param_grads("heads", mid, draw, functools.partial(rt.conv_wgrad, ksize=1), ready=False)      # (the heads lie in the bucket that rpn_conv_3x3 or a layer below it closes)
+        if not self._dgrad_packed:
             rt.pack_conv_dgrad_w(rpn._heads_packed[0], 1, out=self.wd_heads)
         g = rt.conv_ex(draw.reshape(1, NP, H, W), self.wd_heads, self.zero_bias, 1, act=2, mask=mid)
         if self.resnet is not None:
             # ---- rpn_conv_3x3 (g is already under its ReLU mask), then the trunk's own backward pass: res5's ReLU mask is bn3's to apply
-            with _grad_stream(rt, feat, g):
-                rt.conv_wgrad(feat, g, 3, out=self.grad["rpn_conv_3x3/W"])
-                rt.bias_grad(g, out=self.grad["rpn_conv_3x3/b"])
-                self._grads_ready("rpn_conv_3x3")
+            self._param_grads("rpn_conv_3x3", feat, g, rt.conv_wgrad)
             g = rt.conv_ex(g, self.wd["rpn_conv_3x3"], self.zero_bias, 3, act=0)
             rt.mem.join_aux_stream("grad")
             model.trunk.backward(g, self.grad, ready=self._grads_ready)
@@ -735,31 +829,12 @@ class RPNTrainer(_BucketedAllReduce):
                 rt.mem.join_side_stream()
             return dict(losses=losses)
         # ---- rpn_conv_3x3, then the trunk in reverse
-        backward = {"split": trunk_backward_split, "bf16": trunk_backward_bf16, "f16": trunk_backward_bf16}.get(self.conv_math, trunk_backward)
+        backward = trunk_backward if self.arith is None else trunk_backward_operand
         backward(self, list(zip(self.layers, inputs)) + [(("rpn_conv_3x3", 0, 0), feat)], g)
         self._dgrad_packed = False
         if self.run_proposal_layer:
             rt.mem.join_side_stream()
         return dict(losses=losses)
-
-    def update(self):
-        self._ensure_adopted()
-        if self.loss_scaler is not None:
-            # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
-            self.loss_scaler.check(self.G)
-            if self.opt == "MomentumSGD":
-                self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
-            else:                                                     # (Adam: one more one-lane launch, which counts the step unless it is skipped)
-                self._optimizer_step(self.loss_scaler.buf)
-            self.loss_scaler.update()
-            self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
-        elif self.opt == "MomentumSGD":
-            self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
-        else:
-            self._optimizer_step()
-        if hasattr(self.model, "mark_params_updated"):
-            self.model.mark_params_updated(self)
-        self.iteration += 1
 
     def step(self, x, img_info, gt_boxes):
         out = self.forward_backward(x, img_info, gt_boxes)
@@ -774,13 +849,9 @@ class RPNTrainer(_BucketedAllReduce):
 
     # ------------------------------------------------------------------
     def sync_params(self):
-        """Packed training weights -> Chainer-layout arrays on the links (for snapshots / inference objects)."""
-        rt = self.rt
-        for name, link in self.convs:
-            co, ci = link.cout, link.cin
-            link.W = rt.transpose(link.Wp).reshape(co, ci, 3, 3)
+        _Trainer.sync_params(self)
         wp, bp, A = self.model.RPN._heads_packed
-        wt = rt.transpose(wp)                                        # (NP, Cmid)
+        wt = self.rt.transpose(wp)                                   # (NP, Cmid)
         rpn = self.model.RPN
         rpn.rpn_cls_score["W"], rpn.rpn_cls_score["b"] = wt[:2 * A], bp[:2 * A]
         rpn.rpn_bbox_pred["W"], rpn.rpn_bbox_pred["b"] = wt[2 * A:6 * A], bp[2 * A:6 * A]
@@ -788,17 +859,10 @@ class RPNTrainer(_BucketedAllReduce):
     def flat_to_chainer_layout(self, flat):
         """A flat buffer in this trainer's segment layout (gradients, velocities, parameters) -> {link path: host array in
         Chainer's layout}: packed (Cin*9, Cout) -> (Cout, Cin, 3, 3); the stacked heads -> rpn_cls_score / rpn_bbox_pred."""
-        rt, out = self.rt, {}
-        host = rt.mem.to_numpy(flat)
-        def seg(key):
-            sg = self.seg[key]
-            return host[sg.offset:sg.offset + sg.size].reshape(sg.shape)
+        seg, out = self._segment_reader(flat), {}
         if self.resnet is not None:
             self.resnet.to_chainer(seg, out)
-        for name, link in self.convs:
-            prefix = "RPN/" if name == "rpn_conv_3x3" else "trunk/"
-            out[prefix + name + "/W"] = np.ascontiguousarray(seg(name + "/W").T).reshape(link.cout, link.cin, 3, 3)
-            out[prefix + name + "/b"] = seg(name + "/b").copy()
+        self._convs_to_chainer(seg, out)
         A = self.A
         gw, gb = seg("heads/W").T, seg("heads/b")
         out["RPN/rpn_cls_score/W"], out["RPN/rpn_cls_score/b"] = np.ascontiguousarray(gw[:2 * A]).reshape(2 * A, -1, 1, 1), gb[:2 * A].copy()
@@ -807,42 +871,23 @@ class RPNTrainer(_BucketedAllReduce):
 
     def chainer_layout_to_flat(self, arrays, flat):
         """Inverse of flat_to_chainer_layout: write {link path: array} into `flat` (missing keys leave their segment untouched)."""
-        rt = self.rt
-        host = rt.mem.to_numpy(flat).copy()
-        def put(key, val):
-            sg = self.seg[key]
-            host[sg.offset:sg.offset + sg.size] = np.asarray(val, dtype=np.float32).reshape(-1)
-        if self.resnet is not None:
-            self.resnet.from_chainer(arrays, put)
-        for name, link in self.convs:
-            prefix = "RPN/" if name == "rpn_conv_3x3" else "trunk/"
-            if prefix + name + "/W" in arrays:
-                put(name + "/W", np.asarray(arrays[prefix + name + "/W"], dtype=np.float32).reshape(link.cout, -1).T)
-            if prefix + name + "/b" in arrays:
-                put(name + "/b", arrays[prefix + name + "/b"])
-        A = self.A
-        sw, sb = self.seg["heads/W"], self.seg["heads/b"]
-        if "RPN/rpn_cls_score/W" in arrays and "RPN/rpn_bbox_pred/W" in arrays:
-            w = np.zeros((sw.shape[1], sw.shape[0]), np.float32)                       # (NP, Cmid): rows past 6A are channel padding
-            w[:2 * A] = np.asarray(arrays["RPN/rpn_cls_score/W"], dtype=np.float32).reshape(2 * A, -1)
-            w[2 * A:6 * A] = np.asarray(arrays["RPN/rpn_bbox_pred/W"], dtype=np.float32).reshape(4 * A, -1)
-            put("heads/W", w.T)
-            b = np.zeros((sb.shape[0],), np.float32)
-            b[:2 * A], b[2 * A:6 * A] = arrays["RPN/rpn_cls_score/b"], arrays["RPN/rpn_bbox_pred/b"]
-            put("heads/b", b)
-        flat[...] = rt.mem.from_numpy(host)
-
-    def grads_chainer_layout(self):
-        """{link path: gradient in Chainer's layout} (host arrays) -- for tests and inspection.  An fp16 trainer returns UNSCALED gradients:
-        the raw buffer self.G holds S times the gradient (S = the loss scale of the step that filled it); the division is exact."""
-        out = self.flat_to_chainer_layout(self.G)
-        if self.loss_scaler is not None:
-            s = np.float32(self.loss_scaler._words()[1][self._g_scale_word])
-            out = {k: v / s for k, v in out.items()}
-        return out
+        with self._segment_writer(flat) as put:
+            if self.resnet is not None:
+                self.resnet.from_chainer(arrays, put)
+            self._convs_from_chainer(arrays, put)
+            A = self.A
+            sw, sb = self.seg["heads/W"], self.seg["heads/b"]
+            if "RPN/rpn_cls_score/W" in arrays and "RPN/rpn_bbox_pred/W" in arrays:
+                w = np.zeros((sw.shape[1], sw.shape[0]), np.float32)                       # (NP, Cmid): rows past 6A are channel padding
+                w[:2 * A] = np.asarray(arrays["RPN/rpn_cls_score/W"], dtype=np.float32).reshape(2 * A, -1)
+                w[2 * A:6 * A] = np.asarray(arrays["RPN/rpn_bbox_pred/W"], dtype=np.float32).reshape(4 * A, -1)
+                put("heads/W", w.T)
+                b = np.zeros((sb.shape[0],), np.float32)
+                b[:2 * A], b[2 * A:6 * A] = arrays["RPN/rpn_cls_score/b"], arrays["RPN/rpn_bbox_pred/b"]
+                put("heads/b", b)
 
 
-class RCNNTrainer(_BucketedAllReduce):
+class RCNNTrainer(_Trainer):
     """Stage-2 step of train_rcnn.py (train_rcnn.py:35-78; models/faster_rcnn.py:110-173 with rcnn_train = True): trunk -> RPN
     proposals (test-mode ProposalLayer, no gradient) -> RoI pooling -> fc6/fc7 with dropout -> cls_score / bbox_pred ->
     ProposalTargetLayer sampling -> softmax-CE + Huber(1) on the sampled rows -> backward through the head (the four L.Linear
@@ -853,6 +898,8 @@ class RCNNTrainer(_BucketedAllReduce):
     """
 
     HEAD = ("fc6", "fc7", "cls_score", "bbox_pred")
+    stage_hook = None           # bench.py --mode train-rcnn: called with a stage's name at every stage boundary of forward_backward
+    _dropout_iter = None        # dropout_rng="device": the iteration whose forward passes _dropout_fwd counts
 
     def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=None, dropout_ratio=0.5, comm=None, conv_math="mfma", dropout_rng="numpy",
                  dropout_seed=0, precision=None, loss_scale=None, opt="MomentumSGD", opt_args=None):
@@ -892,50 +939,17 @@ class RCNNTrainer(_BucketedAllReduce):
         self.ptl = ProposalTargetLayer(model._feat_stride, num_classes=model._num_classes, runtime=rt)
         self.layers = model.trunk.layers
         self.convs = [(l[0], model.trunk.links[l[0]]) for l in self.layers if l != "pool"]
-        segs, off = {}, 0
-        def add(name, shape):
-            nonlocal off
-            segs[name] = _Seg(name, shape, off)
-            off += (segs[name].size + 63) // 64 * 64
-        for name, link in self.convs:
-            add(name + "/W", link.Wp.shape)
-            add(name + "/b", link.b.shape)
-        for n in self.HEAD:
-            lin = getattr(model, n)
-            add(n + "/W", lin.W.shape)
-            add(n + "/b", lin.b.shape)
-        self.seg, self.n_flat = segs, off
-        self.W, self.G = rt.mem.zeros((off,), "f32"), rt.mem.zeros((off,), "f32")
-        self._alloc_optimizer_state()
-        self._ensure_adopted()
-        self.grad = {k: rt.mem.view(self.G, sg.offset, sg.shape) for k, sg in segs.items()}
-        self.wd = {name: rt.mem.empty((int(link.Wp.shape[1]) * 9, int(link.Wp.shape[0]) // 9), "f32") for name, link in self.convs[1:]}
-        self.zero_bias = rt.mem.zeros((max(512, max(int(getattr(model, n).W.shape[1]) for n in self.HEAD)),), "f32")
-        if conv_math == "split":                                      # split weights of the forward / input-gradient convolutions (re-packed every step)
-            pad = rt.bf16_pad
-            big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
-            self.ws_fwd = {n: rt.mem.empty((3, pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in big}
-            self.ws_dgrad = {n: rt.mem.empty((3, pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in big}
-        self.half = "f16" if precision == "f16" else "bf16"          # the 16-bit operand format of the mixed-precision step
-        self.loss_scaler = None
-        if precision == "f16":
-            kw = dict(loss_scale) if isinstance(loss_scale, dict) else {"loss_scale": "dynamic" if loss_scale is None else loss_scale}
-            self.loss_scaler = LossScaler(rt, **kw)
-            self._g_scale_word = 0                                    # which state word holds the scale self.G is multiplied by
-        if precision is not None:                                     # 16-bit weights of the forward / input-gradient convolutions (re-packed every step)
-            pad = rt.bf16_pad
-            rpn3 = model.RPN.rpn_conv_3x3                             # forward only: stage 2 gives the RPN no gradient
-            self.wb_fwd = {n: rt.mem.empty((pad(l.cin) // 16, 9, pad(l.cout), 16), "i16") for n, l in self.convs + [("rpn_conv_3x3", rpn3)]}
-            self.wb_dgrad = {n: rt.mem.empty((pad(l.cout) // 16, 9, pad(l.cin), 16), "i16") for n, l in self.convs[1:]}
+        head = [getattr(model, n) for n in self.HEAD]
+        self._build_arena(self._conv_segments() + [(n + sfx, a.shape) for n, lin in zip(self.HEAD, head) for sfx, a in (("/W", lin.W), ("/b", lin.b))])
+        rpn3 = [("rpn_conv_3x3", model.RPN.rpn_conv_3x3)] if precision is not None else []      # 16-bit forward only: stage 2 gives the RPN no gradient
+        self._init_arithmetic(precision or conv_math, loss_scale, fwd=self.convs + rpn3, dgrad=self.convs[1:])
+        self.zero_bias = rt.mem.zeros((max(512, max(int(lin.W.shape[1]) for lin in head)),), "f32")
         self.iteration = 0
         # the head (fc6: 411 MB of gradients) is complete before the trunk's backward starts: its bucket rides under all of it
         self._plan_buckets([n for n, _ in self.convs] + list(self.HEAD))
 
     def _ensure_adopted(self):
-        for name, link in self.convs:
-            link.Wp = self._adopt(name + "/W", link.Wp)
-            link.b = self._adopt(name + "/b", link.b)
-            link._adopted = True
+        self._adopt_convs()
         for n in self.HEAD:
             lin = getattr(self.model, n)
             lin.W = self._adopt(n + "/W", lin.W)
@@ -949,13 +963,11 @@ class RCNNTrainer(_BucketedAllReduce):
         lin = getattr(self.model, name)
         M, K = int(x.shape[0]), int(np.prod(x.shape[1:]))
         N = int(dy.shape[1])
-        keep = getattr(self, "keep_dy", None)
-        if keep is not None and name in keep:                        # tests: the (input, upstream gradient) pair a weight gradient was computed from
-            self.kept_dy[name] = (x.reshape(M, K), dy.clone() if hasattr(dy, "clone") else dy.copy())
+        self._tap(name, x.reshape(M, K), dy)
         if self.precision is not None:
             # 16-bit operands: dW = RNE(dy)^T RNE(x) and dx = RNE(dy) RNE(W) with W read as stored -- fp32 arrays in, rounded inside the kernels
             # (csrc/linear_train_bf16.hip): no transposed or padded copies of x, W or dW
-            rth = rt.with_half(self.half)
+            rth = self.arith.rt
             rth.linear_wgrad_bf16(dy, x.reshape(M, K), out=self.grad[name + "/W"])
             rt.bias_grad(rt.transpose(dy).reshape(1, N, 1, M), out=self.grad[name + "/b"])      # db = column sums of dy, as in the fp32 step
             return rth.linear_dgrad_bf16(dy, lin.W) if need_dx else None
@@ -1001,7 +1013,7 @@ class RCNNTrainer(_BucketedAllReduce):
     def forward_backward(self, x, img_info, gt_boxes, masks=None):
         """Fills self.G; returns dict(losses (3,) device [loss_cls, loss_bbox, cls_accuracy], n_rois, keep_inds)."""
         rt, model = self.rt, self.model
-        stage = getattr(self, "stage_hook", None) or (lambda name: None)      # bench.py --mode train-rcnn: a HIP event per stage boundary
+        stage = self.stage_hook or (lambda name: None)               # bench.py --mode train-rcnn: a HIP event per stage boundary
         self._drain()                                              # a previous backward whose sums were never consumed
         self._ensure_adopted()
         x = rt.asarray(unwrap(x), "f32")
@@ -1012,17 +1024,9 @@ class RCNNTrainer(_BucketedAllReduce):
         gt_host = np.ascontiguousarray(rt.mem.to_numpy(gt_host) if rt.mem.is_array(gt_host) else np.asarray(gt_host), dtype=np.float32)
         gt_dev64 = rt.mem.from_numpy_async(np.ascontiguousarray(gt_host[0][:, :4], dtype=np.float64))
         stage("start")
-        if self.conv_math == "split":
-            big = [(n, l) for n, l in self.convs if int(l.cin) > 3]
-            if big:
-                rt.f32s_pack_many([(l.Wp, self.ws_fwd[n], self.ws_dgrad[n], l.cin, l.cout) for n, l in big])
-            feat, inputs, _ = trunk_forward_split(self, x)
-        elif self.precision is not None:
-            # 16-bit weights of every forward / input-gradient convolution (rpn_conv_3x3: forward only) from the current fp32 master weights: one launch
-            rth = rt.with_half(self.half)
-            rpn3 = model.RPN.rpn_conv_3x3
-            rth.bf16_pack_many([(l.Wp, self.wb_fwd[n], self.wb_dgrad.get(n), l.cin, l.cout) for n, l in self.convs + [("rpn_conv_3x3", rpn3)]])
-            feat, inputs, feat_b = trunk_forward_bf16(self, x)
+        if self.arith is not None:                                    # (16-bit: rpn_conv_3x3's forward weights are re-packed with the trunk's)
+            self.arith.repack()
+            feat, inputs, feat_op = trunk_forward_operand(self, x)
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): ONE launch on the gradient
             # stream, under the forward pass -- as in RPNTrainer (one launch per layer inside the backward pass was 12 x 17 us on its critical path)
@@ -1030,11 +1034,12 @@ class RCNNTrainer(_BucketedAllReduce):
                 with _grad_stream(rt):
                     rt.pack_conv_dgrad_w_many([(l.Wp, self.wd[n], 3) for n, l in self.convs[1:]])
                 self._dgrad_packed = True
-            feat, inputs = trunk_forward(model, x, fuse_pools=getattr(self, "keep_dy", None) is None)
+            feat, inputs = trunk_forward(model, x, fuse_pools=self.keep_dy is None)
         C, H, W = [int(v) for v in feat.shape[1:]]
         stage("trunk_fwd")
         if self.precision is not None:                                # rpn_conv_3x3 on the blocked 16-bit map, the 1x1 heads in fp32 (as RPNTrainer)
-            _, mid = rth.conv3x3_bf16_train(feat_b, self.wb_fwd["rpn_conv_3x3"], rpn3.b, rpn3.cin, rpn3.cout, relu=True, want_bf16=False)
+            rpn3 = model.RPN.rpn_conv_3x3
+            _, mid = self.arith.conv(feat_op, self.arith.w_fwd["rpn_conv_3x3"], rpn3.b, rpn3.cin, rpn3.cout, relu=True, want=False)
             _, prob, bbox = rt.rpn_heads(mid, model.RPN._heads_packed)
         else:
             _, _, prob, bbox = model.RPN.heads(feat, want_score=False, wino=False)      # the training step keeps the direct convolution
@@ -1060,7 +1065,7 @@ class RCNNTrainer(_BucketedAllReduce):
             stage("roi_pool_fwd")
             pool5 = pool5.reshape(n, -1)
             if self.precision is not None:                           # the four L.Linear on RNE(x), RNE(W), fp32 accumulation, bias and ReLU
-                rth = rt.with_half(self.half)
+                rth = self.arith.rt
                 fc = lambda lin, xin, relu=False: rth.linear_bf16_train(xin, lin.W, lin.b, relu=relu)
             else:
                 fc = lambda lin, xin, relu=False: lin(xin, relu=relu)
@@ -1071,11 +1076,11 @@ class RCNNTrainer(_BucketedAllReduce):
                 # the stream is a function of (dropout_seed, rank, iteration, forward-within-iteration) -- a trainer rebuilt mid-run (resume: `iteration`
                 # comes back from the snapshot) continues the mask sequence instead of replaying step 0's; the within-iteration index resets when update() advances
                 # `iteration`
-                if getattr(self, "_dropout_iter", None) != self.iteration:
+                if self._dropout_iter != self.iteration:
                     self._dropout_iter, self._dropout_fwd = self.iteration, 0
                 fwd = self._dropout_fwd
                 self._dropout_fwd += 1
-                rank = int(getattr(getattr(self, "comm", None), "rank", 0) or 0)
+                rank = int(getattr(self.comm, "rank", 0) or 0)      # getattr: comm may be None, and a communicator owes the trainers no `rank`
                 base = (self.dropout_seed * 0x100000001b3 + rank * 0x9E3779B97F4A7C15 + (int(self.iteration) << 20) + 2 * fwd) & 0xFFFFFFFFFFFFFFFF
                 d6, m6 = rt.dropout(a6, self.dropout_ratio, base)
             else:
@@ -1163,7 +1168,7 @@ class RCNNTrainer(_BucketedAllReduce):
         gfeat = rt.relu_bwd_(roi_bwd(gp.reshape(rows, C, 7, 7), argmaxb.reshape(rows, C, 7, 7), C, H, W), feat)
         stage("roi_pool_bwd")
         rt.mem.join_aux_stream("grad")                               # the re-packed input-gradient weights are ready
-        backward = trunk_backward_bf16 if self.precision is not None else (trunk_backward_split if self.conv_math == "split" else trunk_backward)
+        backward = trunk_backward if self.arith is None else trunk_backward_operand
         backward(self, list(zip(self.layers, inputs)), gfeat)
         self._dgrad_packed = False
         stage("trunk_bwd")
@@ -1173,25 +1178,6 @@ class RCNNTrainer(_BucketedAllReduce):
         return dict(losses=losses, n_rois=n, keep_inds=keep, masks=(m6, m7), rois=rois, head_acts=(a6, a7), layer_inputs=list(inputs) + [feat], roi_argmax=argmax)       # head_acts: relu(fc6), relu(fc7) before dropout (the parity tests read the device's ReLU decisions off them)
         # layer_inputs / roi_argmax: every discrete decision of this step's forward pass (a fused pool's entry is its _PoolArg: the winning cell and the ReLU bit of
         # every window; an unfused layer's successor input is its post-ReLU map; the arg-max cell of every RoI bin) -- the float64 arbiter of the parity tests imposes them
-
-    def update(self):
-        self._ensure_adopted()
-        if self.loss_scaler is not None:
-            # finite check of the (all-reduced) sums -> the update on G / S, or nothing -> back-off / growth: three launches, the host reads nothing
-            self.loss_scaler.check(self.G)
-            if self.opt == "MomentumSGD":
-                self.rt.sgd_momentum_wd_scaled(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay, self.loss_scaler.buf)
-            else:                                                     # (Adam: one more one-lane launch, which counts the step unless it is skipped)
-                self._optimizer_step(self.loss_scaler.buf)
-            self.loss_scaler.update()
-            self._g_scale_word = 6                                    # self.G is still multiplied by the scale this step used
-        elif self.opt == "MomentumSGD":
-            self.rt.sgd_momentum_wd(self.W, self.G, self.V, self.lr, self.momentum, self.weight_decay)
-        else:
-            self._optimizer_step()
-        if hasattr(self.model, "mark_params_updated"):
-            self.model.mark_params_updated(self)
-        self.iteration += 1
 
     def step(self, x, img_info, gt_boxes, masks=None):
         out = self.forward_backward(x, img_info, gt_boxes, masks)
@@ -1204,46 +1190,19 @@ class RCNNTrainer(_BucketedAllReduce):
         return dict(loss_cls=float(l[0]), loss_bbox=float(l[1]), cls_accuracy=float(l[2]), loss_rcnn=float(l[0] + l[1]))
 
     def flat_to_chainer_layout(self, flat):
-        rt, out = self.rt, {}
-        host = rt.mem.to_numpy(flat)
-        def seg(key):
-            sg = self.seg[key]
-            return host[sg.offset:sg.offset + sg.size].reshape(sg.shape)
-        for name, link in self.convs:
-            out["trunk/" + name + "/W"] = np.ascontiguousarray(seg(name + "/W").T).reshape(link.cout, link.cin, 3, 3)
-            out["trunk/" + name + "/b"] = seg(name + "/b").copy()
+        seg, out = self._segment_reader(flat), {}
+        self._convs_to_chainer(seg, out)
         for n in self.HEAD:
             out[n + "/W"], out[n + "/b"] = seg(n + "/W").copy(), seg(n + "/b").copy()
         return out
 
     def chainer_layout_to_flat(self, arrays, flat):
-        rt = self.rt
-        host = rt.mem.to_numpy(flat).copy()
-        def put(key, val):
-            sg = self.seg[key]
-            host[sg.offset:sg.offset + sg.size] = np.asarray(val, dtype=np.float32).reshape(-1)
-        for name, link in self.convs:
-            if "trunk/" + name + "/W" in arrays:
-                put(name + "/W", np.asarray(arrays["trunk/" + name + "/W"], dtype=np.float32).reshape(link.cout, -1).T)
-            if "trunk/" + name + "/b" in arrays:
-                put(name + "/b", arrays["trunk/" + name + "/b"])
-        for n in self.HEAD:
-            for sfx in ("/W", "/b"):
-                if n + sfx in arrays:
-                    put(n + sfx, arrays[n + sfx])
-        flat[...] = rt.mem.from_numpy(host)
-
-    def grads_chainer_layout(self):
-        """{link path: gradient in Chainer's layout} (host arrays).  An fp16 trainer returns UNSCALED gradients (the division by the power-of-two scale is exact)."""
-        out = self.flat_to_chainer_layout(self.G)
-        if self.loss_scaler is not None:
-            s = np.float32(self.loss_scaler._words()[1][self._g_scale_word])
-            out = {k: v / s for k, v in out.items()}
-        return out
-
-    def sync_params(self):
-        for name, link in self.convs:
-            link.W = self.rt.transpose(link.Wp).reshape(link.cout, link.cin, 3, 3)
+        with self._segment_writer(flat) as put:
+            self._convs_from_chainer(arrays, put)
+            for n in self.HEAD:
+                for sfx in ("/W", "/b"):
+                    if n + sfx in arrays:
+                        put(n + sfx, arrays[n + sfx])
 
 
 class TorchComm(object):
@@ -1262,7 +1221,8 @@ class TorchComm(object):
         import torch.distributed as dist
         self.torch, self.dist, self._time = torch, dist, time
         self.world_size = dist.get_world_size() if dist.is_initialized() else 1
-        # one rank normally skips the exchange; force_single_rank runs it anyway (bench.py --dist-world1, the RCCL smoke test)
+        # `active` is what the trainers ask (every communicator has it; False = skip the exchange): one rank normally skips it;
+        # force_single_rank runs it anyway (bench.py --dist-world1, the RCCL smoke test)
         self.active = dist.is_initialized() and (self.world_size > 1 or force_single_rank)
         self.rank = dist.get_rank() if dist.is_initialized() else 0
         self.backend = dist.get_backend() if dist.is_initialized() else None
