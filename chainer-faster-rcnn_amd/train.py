@@ -245,19 +245,19 @@ def _is_resnet(model):
 
 
 class _ResNetTrunk(object):
-    """What RPNTrainer needs from a ResNet trunk (models/resnet.py), so that one trainer drives both trunk families: the arena segments of its
+    """What a trainer needs from a ResNet trunk (models/resnet.py), so that one trainer drives both trunk families: the arena segments of its
     parameters, their adoption into the arena, forward-with-tape and backward, and the layout conversions of a flat buffer.  Segment keys are
     the link paths below `trunk/` (`conv1/W`, `bn1/gamma`, `res3/a/conv4/W`, ...); a W segment holds the convolution kernels' packed layout.
     The buffer is laid out in EXECUTION order -- a block's projection shortcut conv4 before its conv1 -- so the backward pass fills it from
     the end and the all-reduce's tail buckets close as they do for VGG."""
 
-    def __init__(self, trunk):
+    def __init__(self, trunk, who="RPNTrainer"):
         from .models.resnet import conv_specs
         self.trunk = trunk
         if trunk.conv_dtype != "f32":
-            raise ValueError("RPNTrainer: ResNet training runs on the fp32 trunk (conv_dtype='f32'); mixed-precision ResNet training is not built")
+            raise ValueError("%s: ResNet training runs on the fp32 trunk (conv_dtype='f32'); mixed-precision ResNet training is not built" % who)
         if not trunk.tp:
-            raise ValueError("RPNTrainer: load the model's parameters first")
+            raise ValueError("%s: load the ResNet model's parameters first" % who)
         specs = conv_specs(trunk.blocks, trunk.base_width)
         order, i = [], 0
         while i < len(specs):                                        # (conv1, conv2, conv3, conv4) of a block `a` -> (conv4, conv1, conv2, conv3)
@@ -711,7 +711,7 @@ class RPNTrainer(_Trainer):
         if _is_resnet(model) and conv_math != "mfma":
             raise ValueError("RPNTrainer: a ResNet model trains with conv_math='mfma' (fp32) only, not %r: split-product and mixed-precision "
                              "ResNet training are not built" % (conv_math,))
-        self.resnet = _ResNetTrunk(model.trunk) if _is_resnet(model) else None
+        self.resnet = _ResNetTrunk(model.trunk, "RPNTrainer") if _is_resnet(model) else None
         self.model, self.rt = model, model.rt
         self.lr, self.momentum = lr, momentum
         self._init_optimizer("RPNTrainer", opt, opt_args, weight_decay)      # (AdaGrad / RMSprop: self.lr is the rule's own)
@@ -899,10 +899,11 @@ class RCNNTrainer(_Trainer):
 
     HEAD = ("fc6", "fc7", "cls_score", "bbox_pred")
     stage_hook = None           # bench.py --mode train-rcnn: called with a stage's name at every stage boundary of forward_backward
+    trunk_collect = None        # tests, ResNet model: a dict -> the step's train-mode trunk call fills it (ResNet.__call__(x, collect=...): the taped maps)
     _dropout_iter = None        # dropout_rng="device": the iteration whose forward passes _dropout_fwd counts
 
     def __init__(self, model, lr=0.001, momentum=0.9, weight_decay=None, dropout_ratio=0.5, comm=None, conv_math="mfma", dropout_rng="numpy",
-                 dropout_seed=0, precision=None, loss_scale=None, opt="MomentumSGD", opt_args=None):
+                 dropout_seed=0, precision=None, loss_scale=None, opt="MomentumSGD", opt_args=None, roi_bwd=None):
         """dropout_rng: "numpy" (default) draws both masks on the host from NumPy's global stream exactly as chainer's CPU F.dropout does (two
         np.random.rand calls of n_rois x 4096 values per step: ~7 ms of host time at 300 RoIs, bench.py --mode train-rcnn); "device" draws them
         in the dropout kernel from a counter-based hash of (dropout_seed, step, layer) -- the throughput form, no host work, no H2D.
@@ -916,10 +917,13 @@ class RCNNTrainer(_Trainer):
         device-side loss scale of RPNTrainer(conv_math="f16") (LossScaler): rcnn_loss's two gradient outputs are multiplied by S, self.G holds
         S times the gradient until update(), which skips the step when the all-reduced buffer holds an Inf / NaN.
         loss_scale (precision="f16" only): "dynamic" (the default), a power of two (static), or a dict of LossScaler's constants.
-        opt, opt_args, weight_decay=None: the update rule and its hyper-parameters, as in RPNTrainer."""
+        opt, opt_args, weight_decay=None: the update rule and its hyper-parameters, as in RPNTrainer.
+        roi_bwd: the RoI-pooling scatter, "planes" (csrc/roi_pool.hip: LDS planes, float adds in the order the waves arrive -- two runs agree to rounding) or
+        "ordered" (csrc/roi_bwd_ordered.hip: the reference loop's order of additions, the same bits every run -- what a bit-for-bit resume needs); None = "planes"
+        for the fp32 step, "ordered" for precision="bf16" / "f16" (which always was).
+        A ResNet model (FasterRCNN(trunk_class=ResNet101, rpn_in_ch=2048, feat_stride=32)) trains in fp32 only: conv_math="mfma", precision=None; its trunk runs
+        BatchNormalization on batch statistics (models/resnet.py) and keeps its own tape, the RPN runs in test mode, the head is the code VGG runs."""
         from .models.proposal_target_layer import ProposalTargetLayer
-        if _is_resnet(model):
-            raise ValueError("RCNNTrainer: stage-2 training of a ResNet model is not built (RPNTrainer trains its trunk and RPN)")
         if conv_math not in ("mfma", "split"):
             raise ValueError("RCNNTrainer: conv_math is the arithmetic of the trunk's fp32 convolutions, 'mfma' or 'split', not %r "
                              "(16-bit operands: precision='bf16' / 'f16')" % (conv_math,))
@@ -929,7 +933,17 @@ class RCNNTrainer(_Trainer):
             raise ValueError("RCNNTrainer: precision=%r replaces the fp32 convolutions; it does not combine with conv_math='split'" % (precision,))
         if loss_scale is not None and precision != "f16":
             raise ValueError("RCNNTrainer: loss_scale belongs to precision='f16', not %r" % (precision,))
+        if roi_bwd not in (None, "planes", "ordered"):
+            raise ValueError("RCNNTrainer: roi_bwd must be None, 'planes' or 'ordered', not %r" % (roi_bwd,))
+        if _is_resnet(model):
+            if conv_math != "mfma" or precision is not None:
+                raise ValueError("RCNNTrainer: a ResNet model trains with conv_math='mfma' and precision=None (fp32) only, not conv_math=%r, precision=%r: "
+                                 "split-product and mixed-precision ResNet training are not built" % (conv_math, precision))
+            if any(getattr(model, n).W is None or getattr(model, n).b is None for n in self.HEAD):        # (before anything is allocated)
+                raise ValueError("RCNNTrainer: this ResNet model's head (fc6, fc7, cls_score, bbox_pred) holds no parameters; load them first")
+        self.resnet = _ResNetTrunk(model.trunk, "RCNNTrainer") if _is_resnet(model) else None
         self.conv_math, self.precision = conv_math, precision
+        self.roi_bwd = roi_bwd or ("ordered" if precision is not None else "planes")
         self.model, self.rt = model, model.rt
         self.lr, self.momentum, self.dropout_ratio, self.comm = lr, momentum, dropout_ratio, comm
         self._init_optimizer("RCNNTrainer", opt, opt_args, weight_decay)
@@ -937,18 +951,22 @@ class RCNNTrainer(_Trainer):
         self.dropout_rng, self.dropout_seed = dropout_rng, int(dropout_seed)
         rt = self.rt
         self.ptl = ProposalTargetLayer(model._feat_stride, num_classes=model._num_classes, runtime=rt)
-        self.layers = model.trunk.layers
+        # (a ResNet trunk's parameters are not `links`: self.resnet lays them out, in execution order, and the trunk re-packs its own input-gradient weights)
+        self.layers = model.trunk.layers if self.resnet is None else []
         self.convs = [(l[0], model.trunk.links[l[0]]) for l in self.layers if l != "pool"]
         head = [getattr(model, n) for n in self.HEAD]
-        self._build_arena(self._conv_segments() + [(n + sfx, a.shape) for n, lin in zip(self.HEAD, head) for sfx, a in (("/W", lin.W), ("/b", lin.b))])
+        self._build_arena((self.resnet.segments() if self.resnet is not None else []) + self._conv_segments()
+                          + [(n + sfx, a.shape) for n, lin in zip(self.HEAD, head) for sfx, a in (("/W", lin.W), ("/b", lin.b))])
         rpn3 = [("rpn_conv_3x3", model.RPN.rpn_conv_3x3)] if precision is not None else []      # 16-bit forward only: stage 2 gives the RPN no gradient
         self._init_arithmetic(precision or conv_math, loss_scale, fwd=self.convs + rpn3, dgrad=self.convs[1:])
         self.zero_bias = rt.mem.zeros((max(512, max(int(lin.W.shape[1]) for lin in head)),), "f32")
         self.iteration = 0
         # the head (fc6: 411 MB of gradients) is complete before the trunk's backward starts: its bucket rides under all of it
-        self._plan_buckets([n for n, _ in self.convs] + list(self.HEAD))
+        self._plan_buckets((self.resnet.names if self.resnet is not None else []) + [n for n, _ in self.convs] + list(self.HEAD))
 
     def _ensure_adopted(self):
+        if self.resnet is not None:
+            self.resnet.adopt(self)
         self._adopt_convs()
         for n in self.HEAD:
             lin = getattr(self.model, n)
@@ -1027,6 +1045,10 @@ class RCNNTrainer(_Trainer):
         if self.arith is not None:                                    # (16-bit: rpn_conv_3x3's forward weights are re-packed with the trunk's)
             self.arith.repack()
             feat, inputs, feat_op = trunk_forward_operand(self, x)
+        elif self.resnet is not None:
+            # train-mode BatchNormalization trunk: the forward pass keeps its own tape (and moves the running statistics); its input-gradient packings are its own
+            model.trunk.train = True
+            feat, inputs = (model.trunk(x, collect=self.trunk_collect) if self.trunk_collect is not None else model.trunk(x)), []
         else:
             # weights of every input-gradient convolution (rotated / transposed copies of the current packed weights): ONE launch on the gradient
             # stream, under the forward pass -- as in RPNTrainer (one launch per layer inside the backward pass was 12 x 17 us on its critical path)
@@ -1164,20 +1186,29 @@ class RCNNTrainer(_Trainer):
         # ---- RoI pooling (arg-max scatter) and the trunk; feat = relu(conv5_3): mask before entering conv5_3's backward
         # (16-bit step: this map is rounded for conv5_3's backward products, where the last bit of a cell can decide a rounding -- the scatter with a fixed order
         # of additions keeps two steps from one state bit-identical; the fp32 step keeps its plane kernel, whose float atomics stay at rounding level)
-        roi_bwd = rt.roi_pool_bwd_ordered if self.precision is not None else rt.roi_pool_bwd
-        gfeat = rt.relu_bwd_(roi_bwd(gp.reshape(rows, C, 7, 7), argmaxb.reshape(rows, C, 7, 7), C, H, W), feat)
-        stage("roi_pool_bwd")
-        rt.mem.join_aux_stream("grad")                               # the re-packed input-gradient weights are ready
-        backward = trunk_backward if self.arith is None else trunk_backward_operand
-        backward(self, list(zip(self.layers, inputs)), gfeat)
-        self._dgrad_packed = False
+        roi_bwd = rt.roi_pool_bwd_ordered if self.roi_bwd == "ordered" else rt.roi_pool_bwd
+        gfeat = roi_bwd(gp.reshape(rows, C, 7, 7), argmaxb.reshape(rows, C, 7, 7), C, H, W)
+        if self.resnet is not None:
+            # dL/d res5 goes in UNMASKED: res5 = relu(bn3(conv3) + shortcut), and bn3's backward applies that ReLU's mask (models/resnet.py ResNet.backward)
+            stage("roi_pool_bwd")
+            model.trunk.backward(gfeat, self.grad, ready=self._grads_ready)
+        else:
+            gfeat = rt.relu_bwd_(gfeat, feat)
+            stage("roi_pool_bwd")
+            rt.mem.join_aux_stream("grad")                           # the re-packed input-gradient weights are ready
+            backward = trunk_backward if self.arith is None else trunk_backward_operand
+            backward(self, list(zip(self.layers, inputs)), gfeat)
+            self._dgrad_packed = False
         stage("trunk_bwd")
         # rois: the (n, 4) proposals THIS step pooled -- a parity test must hand the oracle these, not the proposals of a second, inference-form forward: the
         # fused conv + ReLU + pool launches of the training forward (act 5) and of the inference forward (act 4) may run different decompositions (round 6:
         # pick_conv_config), i.e. conv5_3 agrees to the last bits but one, and near-tied proposals can then differ
-        return dict(losses=losses, n_rois=n, keep_inds=keep, masks=(m6, m7), rois=rois, head_acts=(a6, a7), layer_inputs=list(inputs) + [feat], roi_argmax=argmax)       # head_acts: relu(fc6), relu(fc7) before dropout (the parity tests read the device's ReLU decisions off them)
+        # head_acts: relu(fc6), relu(fc7) before dropout (the parity tests read the device's ReLU decisions off them)
         # layer_inputs / roi_argmax: every discrete decision of this step's forward pass (a fused pool's entry is its _PoolArg: the winning cell and the ReLU bit of
         # every window; an unfused layer's successor input is its post-ReLU map; the arg-max cell of every RoI bin) -- the float64 arbiter of the parity tests imposes them
+        # (a ResNet model: layer_inputs is [] -- the trunk's tape is the record of its decisions, self.trunk_collect receives its maps)
+        layer_inputs = (list(inputs) + [feat]) if self.resnet is None else []
+        return dict(losses=losses, n_rois=n, keep_inds=keep, masks=(m6, m7), rois=rois, head_acts=(a6, a7), layer_inputs=layer_inputs, roi_argmax=argmax)
 
     def step(self, x, img_info, gt_boxes, masks=None):
         out = self.forward_backward(x, img_info, gt_boxes, masks)
@@ -1191,6 +1222,8 @@ class RCNNTrainer(_Trainer):
 
     def flat_to_chainer_layout(self, flat):
         seg, out = self._segment_reader(flat), {}
+        if self.resnet is not None:
+            self.resnet.to_chainer(seg, out)
         self._convs_to_chainer(seg, out)
         for n in self.HEAD:
             out[n + "/W"], out[n + "/b"] = seg(n + "/W").copy(), seg(n + "/b").copy()
@@ -1198,6 +1231,8 @@ class RCNNTrainer(_Trainer):
 
     def chainer_layout_to_flat(self, arrays, flat):
         with self._segment_writer(flat) as put:
+            if self.resnet is not None:
+                self.resnet.from_chainer(arrays, put)
             self._convs_from_chainer(arrays, put)
             for n in self.HEAD:
                 for sfx in ("/W", "/b"):
