@@ -167,6 +167,12 @@ SIGNATURES = {
     "frcnn_conv1x1_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _S, _P]),
     "frcnn_im2col7x7s2_f16": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "frcnn_maxpool3x3s2_f16": (_I, [_P, _P, _I, _I, _I, _P]),
+    "frcnn_conv1x1_fwd_bf16_train_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_conv1x1_fwd_bf16_train": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _S, _P]),
+    "frcnn_conv1x1_dgrad_bf16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_conv1x1_dgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
+    "frcnn_conv1x1_wgrad_bf16_workspace_bytes": (_S, [_I, _I, _I]),
+    "frcnn_conv1x1_wgrad_bf16": (_I, [_P, _P, _P, _I, _I, _I, _P, _S, _P]),
     "frcnn_subsample2_f32": (_I, [_P, _P, _I, _I, _I, _P]),
     "frcnn_bn_workspace_bytes": (_S, [_I, _I]),
     "frcnn_bn_train_fwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _S, _P]),

@@ -16,7 +16,18 @@ runs on the statistics of the map it is given (csrc/bn_train.hip): each convolut
 normalises its output with the ReLU -- and in a bottleneck tail the shortcut sum -- fused, and updates the running statistics.  The call
 keeps a tape (conv inputs, pre-BN maps z, outputs y, saved mean and 1/std); `backward(g, grads)` walks it in reverse and fills the gradient
 of every W (packed layout), gamma, beta and `conv1/b`.  `mark_params_updated()` re-folds the inference weights from the current parameters
-and running statistics.  The 16-bit trunks are inference-only.
+and running statistics.  The 16-bit trunks (conv_dtype) are inference-only.
+
+Training on bf16 operands: train_dtype="bf16" (with conv_dtype="f32"; parameters stay the fp32 master copies in `tp`).  The trunk owns its tape and its
+backward pass, so it owns the arithmetic of its train-mode pass, as it owns conv_dtype for inference; a trainer's conv_math / precision stay the
+arithmetic of the trainer's own links.  In the train-mode pass every convolution PRODUCT then runs on bf16 operands with fp32 accumulation -- the forward
+pass of every layer, the input gradient of every layer but the stem, the weight gradient of every layer -- each operand the round-to-nearest-even image
+of the fp32 tensor the tape holds (x, the master W, dz).  1x1 layers and the stem (over its fp32 im2col columns) run csrc/conv1x1_train_bf16.hip, which
+rounds while it stages: no per-step weight re-pack, the input gradient reads the forward pass's packed weights.  The 3x3 conv2 layers run
+frcnn_bf16_from_nchw_f32 + frcnn_conv3x3_bf16_train (forward, and the input gradient on input-gradient weights) and frcnn_conv_wgrad_bf16; their 16-bit
+weights are re-packed once after an update, sixteen layers per launch (frcnn_bf16_pack_many).  Everything else is the fp32 step's: im2col, conv1/b and
+the bias gradient, BatchNorm forward and backward on the fp32 pre-BN maps, ReLU masks, pooling, subsampling, shortcut adds, the tape, the running
+statistics, the re-fold.  The test-mode pass and the fp32 train-mode pass are untouched.
 
 conv_dtype="bf16" runs the trunk on the 16-bit chain (channel-blocked [C/16][H][W][16] maps, operands rounded to nearest even, fp32
 accumulation): the stem as frcnn_im2col7x7s2_bf16 + the 1x1 kernel (Kp = 160), frcnn_maxpool3x3s2_bf16, every 1x1 (stride 2 folded into
@@ -101,12 +112,18 @@ class _FoldedConv(object):
 
 
 class ResNet(object):
-    def __init__(self, n_layers=101, runtime=None, blocks=None, conv_dtype="f32", base_width=64):
+    def __init__(self, n_layers=101, runtime=None, blocks=None, conv_dtype="f32", base_width=64, train_dtype="f32"):
         if conv_dtype == "f32s":
             raise ValueError("ResNet: conv_dtype 'f32s' (split-product fp32) is not implemented for the ResNet trunk; use 'f32' or 'bf16'")
         if conv_dtype not in ("f32", "bf16"):
             raise ValueError("ResNet: conv_dtype must be 'f32' or 'bf16' (fp16: a with_half('f16') runtime), not %r" % (conv_dtype,))
+        if train_dtype not in ("f32", "bf16"):
+            raise ValueError("ResNet: train_dtype must be 'f32' or 'bf16' (fp16 training needs a loss scale: not built), not %r" % (train_dtype,))
+        if train_dtype == "bf16" and conv_dtype != "f32":
+            raise ValueError("ResNet: train_dtype='bf16' needs conv_dtype='f32' (the train-mode pass rounds the fp32 master parameters; the 16-bit "
+                             "inference trunks hold none), not conv_dtype=%r" % (conv_dtype,))
         self.rt = runtime or default_runtime()
+        self.train_dtype = train_dtype
         self.blocks = tuple(blocks) if blocks is not None else BLOCKS[n_layers]
         self.conv_dtype = conv_dtype
         if int(base_width) < 64 or int(base_width) % 64:
@@ -119,6 +136,7 @@ class ResNet(object):
         self.tp = {}                                           # train-mode parameters on the device, by link path below the prefix
         self.tape = None
         self._wd, self._wd_stale = {}, True                    # input-gradient packings of tp's weights, re-packed after an update
+        self._w16, self._w16_stale = {}, True                  # train_dtype "bf16": 16-bit forward / input-gradient weights of the 3x3 layers
         self._zero_bias = {}
         self._fold_stale = False
         self.skip_nchw = False
@@ -138,6 +156,7 @@ class ResNet(object):
                 if (prefix + conv + "/b") in params:
                     self.tp[conv + "/b"] = m.from_numpy(np.ascontiguousarray(params[prefix + conv + "/b"], dtype=np.float32))
         self._wd, self._wd_stale = {}, True
+        self._w16, self._w16_stale = {}, True
         self._fold_stale = False
 
     # ---- the trainable form ---------------------------------------------------------------------------------------------------------------
@@ -160,6 +179,7 @@ class ResNet(object):
         """the parameters (or running statistics) changed on the device: the input-gradient packings are rebuilt at the next backward pass and the
         folded inference weights at the next test-mode call"""
         self._wd_stale = True
+        self._w16_stale = True
         self._fold_stale = True
 
     def params_host(self, prefix="trunk/"):
@@ -191,11 +211,39 @@ class ResNet(object):
         rt, tp = self.rt, self.tp
         W = tp[conv + "/W"]
         co = int(W.shape[1])
-        z = rt.conv_ex(x, W, tp.get(conv + "/b", self._zeros(co)), ksize, act=0)
+        if self.train_dtype == "bf16":
+            z = self._conv16(conv, x, W, ksize)
+        else:
+            z = rt.conv_ex(x, W, tp.get(conv + "/b", self._zeros(co)), ksize, act=0)
         y, mean, rstd = rt.bn_train_fwd(z, tp[bn + "/gamma"], tp[bn + "/beta"], residual=residual, relu=relu, eps=BN_EPS, decay=BN_DECAY,
                                         running_mean=tp[bn + "/avg_mean"], running_var=tp[bn + "/avg_var"])
         self.tape[conv] = dict(x=x, z=z, y=y, mean=mean, rstd=rstd, relu=relu, bn=bn, ksize=ksize)
         return y
+
+    def _w16_of(self, conv):
+        """(forward, input-gradient) 16-bit weights of a 3x3 layer from the current master weights; after an update ALL 3x3 layers are re-packed at the
+        first request, sixteen per launch (frcnn_bf16_pack_many), into buffers that are kept -- _dgrad_w's scheme"""
+        if self._w16_stale:
+            rt, todo = self.rt.with_half("bf16"), []
+            pad = rt.bf16_pad
+            for c, _, ci, co, k in conv_specs(self.blocks, self.base_width):
+                if k != 3:
+                    continue
+                if c not in self._w16:
+                    self._w16[c] = (rt.mem.empty((pad(ci) // 16, 9, pad(co), 16), "i16"), rt.mem.empty((pad(co) // 16, 9, pad(ci), 16), "i16"))
+                todo.append((self.tp[c + "/W"], self._w16[c][0], self._w16[c][1], ci, co))
+            for i in range(0, len(todo), 16):
+                rt.bf16_pack_many(todo[i:i + 16])
+            self._w16_stale = False
+        return self._w16[conv]
+
+    def _conv16(self, conv, x, W, ksize):
+        """the pre-BN map of one layer on bf16 products: z = conv(RNE(x), RNE(W)) (+ conv1/b), fp32 accumulation"""
+        rt = self.rt.with_half("bf16")
+        if ksize == 1:
+            return rt.conv1x1_bf16_train(x, W, self.tp.get(conv + "/b"))
+        ci, co = int(x.shape[1]), int(W.shape[1])
+        return rt.conv3x3_bf16_train(rt.bf16_from_nchw(x), self._w16_of(conv)[0], self._zeros(co), ci, co, relu=False, want_bf16=False)[1]
 
     def _call_train(self, h, timer=None, collect=None):
         rt = self.rt
@@ -236,14 +284,20 @@ class ResNet(object):
             self._wd_stale = False
         return self._wd[conv]
 
-    def _conv_bn_bwd(self, conv, dy, grads, want_dres=False, want_dx=True, ready=None):
+    def _conv_bn_bwd(self, conv, dy, grads, want_dres=False, want_dx=True, ready=None, collect=None):
         """backward of _conv_bn: fills grads[conv/W], grads[bn/gamma], grads[bn/beta] -> (dL/dx or None, dres or None)"""
         rt, t = self.rt, self.tape[conv]
         bn, ks = t["bn"], t["ksize"]
         dz, dg, db, dres = rt.bn_train_bwd(dy, t["y"] if t["relu"] else None, t["z"], self.tp[bn + "/gamma"], t["mean"], t["rstd"], want_dres=want_dres,
                                            dgamma=grads.get(bn + "/gamma"), dbeta=grads.get(bn + "/beta"))
         grads[bn + "/gamma"], grads[bn + "/beta"] = dg, db
-        grads[conv + "/W"] = rt.conv_wgrad(t["x"], dz, ks, out=grads.get(conv + "/W"))
+        bf16 = self.train_dtype == "bf16"
+        if bf16:
+            rt16 = rt.with_half("bf16")
+            wgrad = rt16.conv1x1_wgrad_bf16 if ks == 1 else rt16.conv_wgrad_bf16
+            grads[conv + "/W"] = wgrad(t["x"], dz, out=grads.get(conv + "/W"))
+        else:
+            grads[conv + "/W"] = rt.conv_wgrad(t["x"], dz, ks, out=grads.get(conv + "/W"))
         if (conv + "/b") in self.tp:
             grads[conv + "/b"] = rt.bias_grad(dz, out=grads.get(conv + "/b"))
         if ready is not None:
@@ -251,13 +305,23 @@ class ResNet(object):
         dx = None
         if want_dx:
             ci = int(t["x"].shape[1])
-            dx = rt.conv_ex(dz, self._dgrad_w(conv, ks), self._zeros(ci), ks, act=0)
+            if bf16 and ks == 1:
+                dx = rt16.conv1x1_dgrad_bf16(dz, self.tp[conv + "/W"])
+            elif bf16:
+                dx = rt16.conv3x3_bf16_train(rt16.bf16_from_nchw(dz), self._w16_of(conv)[1], self._zeros(ci), int(dz.shape[1]), ci, relu=False,
+                                             want_bf16=False)[1]
+            else:
+                dx = rt.conv_ex(dz, self._dgrad_w(conv, ks), self._zeros(ci), ks, act=0)
+        if collect is not None:
+            collect[conv] = (dy, dz, dx)
         return dx, dres
 
-    def backward(self, g, grads=None, ready=None):
+    def backward(self, g, grads=None, ready=None, collect=None):
         """g = dL/d res5 of the last train-mode call -> grads: {key below the prefix: device array}, the gradient of every W (in the packed
         layout of tp), gamma, beta and conv1/b.  Arrays already present in `grads` are written in place (a trainer's arena views); `ready(conv)`
-        is called once a layer's gradients are enqueued, in reverse execution order (conv3, conv2, conv1, conv4 within a block `a`)."""
+        is called once a layer's gradients are enqueued, in reverse execution order (conv3, conv2, conv1, conv4 within a block `a`).  `collect`
+        (optional dict, tests) receives per convolution (dy into its BN, dz = the pre-BN map's gradient, dx or None for the stem) and per block
+        `res3/a/` (the shortcut's gradient, dL/d(block input))."""
         rt = self.rt
         if self.tape is None:
             raise ValueError("ResNet.backward: no train-mode forward pass to differentiate")
@@ -267,19 +331,23 @@ class ResNet(object):
             for b in reversed(block_names(n)):
                 p = "%s/%s/" % (stage, b)
                 # g = dL/d(block output); its ReLU mask is applied by bn3's backward, which also hands back dres = the shortcut's gradient
-                d, dres = self._conv_bn_bwd(p + "conv3", g, grads, want_dres=True, ready=ready)
-                d, _ = self._conv_bn_bwd(p + "conv2", d, grads, ready=ready)
-                d, _ = self._conv_bn_bwd(p + "conv1", d, grads, ready=ready)
+                d, dres = self._conv_bn_bwd(p + "conv3", g, grads, want_dres=True, ready=ready, collect=collect)
+                d, _ = self._conv_bn_bwd(p + "conv2", d, grads, ready=ready, collect=collect)
+                d, _ = self._conv_bn_bwd(p + "conv1", d, grads, ready=ready, collect=collect)
                 if b == "a":
-                    d4, _ = self._conv_bn_bwd(p + "conv4", dres, grads, ready=ready)
-                    d = rt.add(d, d4, out=d)
+                    d4, _ = self._conv_bn_bwd(p + "conv4", dres, grads, ready=ready, collect=collect)
+                    other = d4
+                    d = rt.add(d, d4, out=None if collect is not None else d)      # (collected: the layers' own dx stay as they were written)
                     if self.tape[p]["strided"]:
                         d = rt.subsample2_bwd(d, *self.tape[p]["hw"])
                 else:
-                    d = rt.add(d, dres, out=d)                 # the identity shortcut
+                    other = dres
+                    d = rt.add(d, dres, out=None if collect is not None else d)    # the identity shortcut
+                if collect is not None:
+                    collect[p] = (other, d)                    # the shortcut's gradient and dL/d(block input)
                 g = d
         g = rt.maxpool3x3s2_bwd(self.tape["conv1"]["y"], g)
-        self._conv_bn_bwd("conv1", g, grads, want_dx=False, ready=ready)     # the image needs no gradient
+        self._conv_bn_bwd("conv1", g, grads, want_dx=False, ready=ready, collect=collect)     # the image needs no gradient
         return grads
 
     def _conv(self, name, x, act=1, residual=None):
@@ -292,7 +360,8 @@ class ResNet(object):
         assert h.ndim == 4 and int(h.shape[0]) == 1, "batch size 1 (models/faster_rcnn.py:77)"
         if self.train:
             if self.conv_dtype != "f32":
-                raise ValueError("ResNet: train-mode BatchNormalization runs on the fp32 trunk only (conv_dtype='f32'); the 16-bit trunks are inference-only")
+                raise ValueError("ResNet: train-mode BatchNormalization runs on the fp32 trunk only (conv_dtype='f32'); the 16-bit trunks are inference-only "
+                                 "(bf16 training: conv_dtype='f32' with train_dtype='bf16')")
             return self._call_train(h, timer, collect)
         if self.conv_dtype == "bf16":
             return self._call_bf16(h, timer, collect)

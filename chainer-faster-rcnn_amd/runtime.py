@@ -196,6 +196,7 @@ class Runtime(object):
         self.lib = lib
         self.mem = mem
         self._ws = {}
+        self._c1t_sizes = {}                   # workspace sizes of the 1x1 training entries by (entry, shape, tuning state); shared by with_half copies
         assert half in ("bf16", "f16")
         self.half = half                       # the 16-bit operand format the *_bf16 methods below compute in
         self.hlib = _HalfLib(lib, half)
@@ -709,6 +710,59 @@ class Runtime(object):
         ws = self.workspace("wgrad_bf16", L.frcnn_conv_wgrad_bf16_workspace_bytes(ci, co, H, W))
         _lib.check(L.frcnn_conv_wgrad_bf16(m.ptr(x), m.ptr(dy), m.ptr(dw), ci, co, H, W, m.ptr(ws), ws.shape[0], m.stream()),
                    "frcnn_conv_wgrad_bf16")
+        return dw
+
+    # the ResNet trunk's 1x1 convolutions in training form (csrc/conv1x1_train_bf16.hip; ResNet(train_dtype="bf16")): fp32 maps and fp32 master weights in,
+    # rounded to bf16 inside the kernels, fp32 out.  bf16 only: these entries have no fp16 twin (self.lib, not self.hlib)
+    def _c1t_workspace(self, size_fn, ci, co, hw):
+        """the entries' workspace; its size per (entry, shape) is asked of the library once per state of the three tuning keys its plan reads"""
+        key = (size_fn.__name__, ci, co, hw, _tuning.get("FRCNN_C1T_SPLIT"), _tuning.get("FRCNN_C1T_WGRAD_SPLITS"), _tuning.get("FRCNN_C1T_MT"))
+        nbytes = self._c1t_sizes.get(key)
+        if nbytes is None:
+            nbytes = self._c1t_sizes[key] = max(int(size_fn(ci, co, hw)), 65536)
+        w = self._ws.get("conv1x1_train")
+        if w is not None and w.shape[0] >= nbytes:
+            return w
+
+        def init(w):                                           # the counter page: zeroed once per allocation, left zero by every launch
+            w[:65536] = 0
+        return self.workspace("conv1x1_train", nbytes, init=init)
+
+    def conv1x1_bf16_train(self, x, w_packed, bias=None):
+        """z[co][p] = sum_ci RNE(W[ci][co]) RNE(x[ci][p]) (+ bias[co]): x (1,Cin,H,W) fp32, w_packed (Cin,Cout) fp32 -> (1,Cout,H,W) fp32."""
+        m, L = self.mem, self.lib
+        ci, H, W = [int(v) for v in x.shape[-3:]]
+        co = int(w_packed.shape[1])
+        assert int(w_packed.shape[0]) == ci
+        z = m.empty((1, co, H, W), "f32")
+        ws = self._c1t_workspace(L.frcnn_conv1x1_fwd_bf16_train_workspace_bytes, ci, co, H * W)
+        _lib.check(L.frcnn_conv1x1_fwd_bf16_train(m.ptr(x), m.ptr(w_packed), m.ptr(bias), m.ptr(z), ci, co, H * W, m.ptr(ws), ws.shape[0], m.stream()),
+                   "frcnn_conv1x1_fwd_bf16_train")
+        return z
+
+    def conv1x1_dgrad_bf16(self, dz, w_packed):
+        """dx[ci][p] = sum_co RNE(W[ci][co]) RNE(dz[co][p]): the forward pass's packed weights, read as stored."""
+        m, L = self.mem, self.lib
+        co, H, W = [int(v) for v in dz.shape[-3:]]
+        ci = int(w_packed.shape[0])
+        assert int(w_packed.shape[1]) == co
+        dx = m.empty((1, ci, H, W), "f32")
+        ws = self._c1t_workspace(L.frcnn_conv1x1_dgrad_bf16_workspace_bytes, ci, co, H * W)
+        _lib.check(L.frcnn_conv1x1_dgrad_bf16(m.ptr(dz), m.ptr(w_packed), m.ptr(dx), ci, co, H * W, m.ptr(ws), ws.shape[0], m.stream()),
+                   "frcnn_conv1x1_dgrad_bf16")
+        return dx
+
+    def conv1x1_wgrad_bf16(self, x, dz, out=None):
+        """dW[ci][co] = sum_p RNE(x[ci][p]) RNE(dz[co][p]) in the packed (Cin,Cout) layout; slabs over the pixel axis added in a fixed order."""
+        m, L = self.mem, self.lib
+        ci, H, W = [int(v) for v in x.shape[-3:]]
+        co = int(dz.shape[-3])
+        assert (int(dz.shape[-2]), int(dz.shape[-1])) == (H, W)
+        dw = out if out is not None else m.empty((ci, co), "f32")
+        assert tuple(int(v) for v in dw.shape) == (ci, co)
+        ws = self._c1t_workspace(L.frcnn_conv1x1_wgrad_bf16_workspace_bytes, ci, co, H * W)
+        _lib.check(L.frcnn_conv1x1_wgrad_bf16(m.ptr(x), m.ptr(dz), m.ptr(dw), ci, co, H * W, m.ptr(ws), ws.shape[0], m.stream()),
+                   "frcnn_conv1x1_wgrad_bf16")
         return dw
 
     # L.Linear of the mixed-precision stage-2 step (csrc/linear_train_bf16.hip): fp32 arrays in, rounded inside the kernels, fp32 out

@@ -388,6 +388,30 @@ int frcnn_linear_dgrad_bf16(const float *dy, const float *w, float *dx, int M, i
 size_t frcnn_linear_wgrad_bf16_workspace_bytes(int M, int N, int K);
 int frcnn_linear_wgrad_bf16(const float *dy, const float *x, float *dw, int M, int N, int K, void *workspace, size_t workspace_bytes,
                             void *stream);
+/* ---- the 1x1 convolution of the ResNet trunk in training form on bf16 operands (csrc/conv1x1_train_bf16.hip; ResNet(train_dtype="bf16")) ---------------------
+ * Forward, input gradient and weight gradient of the L.Convolution2D 1x1 forward / backward inside chainer's ResNetLayers, /root/reference/models/resnet.py:11-45
+ * (and of the 7x7 stem over its im2col columns), as GEMMs over the flat pixel axis of (C, HW) row-major fp32 maps: bf16 products, fp32 accumulation.  Every
+ * operand is an fp32 array -- x (Cin, HW), dz (Cout, HW), the fp32 master weights in the packed (Cin, Cout) layout -- rounded to nearest even inside the
+ * kernel while it is staged; outputs are fp32.  Stride never enters: frcnn_subsample2_f32 / frcnn_subsample2_bwd_f32 stay in front of a strided layer.
+ *   forward          z[co][p]   = sum_ci RNE(W[ci][co]) RNE(x[ci][p]) (+ b[co]; bias (Cout) or NULL)
+ *   input gradient   dx[ci][p]  = sum_co RNE(W[ci][co]) RNE(dz[co][p])
+ *   weight gradient  dW[ci][co] = sum_p  RNE(x[ci][p]) RNE(dz[co][p])
+ * Every dimension is ragged (all accesses are range-checked 4-byte buffer accesses: no alignment beyond 4 bytes is assumed).  The workspace starts with a
+ * 64 KB counter page that the CALLER zeroes once and every launch leaves zero; behind it the forward / input gradient keep the slots of an in-launch K
+ * split (the last arriver adds all slots in split order) and the weight gradient its slabs (a second launch adds them in slab order).  No atomics on
+ * data: two calls on the same inputs give identical bits.  FRCNN_ERR_INVALID, and nothing launched, for a NULL required pointer, a dimension < 1, an
+ * operand of 2^31 bytes or more, a NULL or too small workspace (the companions return the size; 0 for invalid dimensions).  Tuning keys (A/B and
+ * tests): FRCNN_C1T_SPLIT (forward / input gradient), FRCNN_C1T_WGRAD_SPLITS: the number of pieces, capped by the number of 64-deep chunks;
+ * FRCNN_C1T_MT = 2 / 4: the workgroup tile's rows / 32 (default 2; 4 for launches of more than eight 64-row tiles per CU). */
+size_t frcnn_conv1x1_fwd_bf16_train_workspace_bytes(int Cin, int Cout, int HW);
+int frcnn_conv1x1_fwd_bf16_train(const float *x, const float *w_packed, const float *bias, float *z, int Cin, int Cout, int HW, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+size_t frcnn_conv1x1_dgrad_bf16_workspace_bytes(int Cin, int Cout, int HW);
+int frcnn_conv1x1_dgrad_bf16(const float *dz, const float *w_packed, float *dx, int Cin, int Cout, int HW, void *workspace, size_t workspace_bytes,
+                             void *stream);
+size_t frcnn_conv1x1_wgrad_bf16_workspace_bytes(int Cin, int Cout, int HW);
+int frcnn_conv1x1_wgrad_bf16(const float *x, const float *dz, float *dw_packed, int Cin, int Cout, int HW, void *workspace, size_t workspace_bytes,
+                             void *stream);
 /* RoI max-pooling backward with a fixed order of additions (csrc/roi_bwd_ordered.hip): frcnn_roi_pool_bwd's arguments and result -- the backward of
  * F.roi_pooling_2d, call site models/faster_rcnn.py:125-126 -- with every cell's sum taken over the RoIs in ascending order and, within a RoI, the bins in ascending
  * order (the reference's CPU loop order); no atomics, identical bits from run to run.  The mixed-precision stage-2 step uses it: its result is rounded to 16
